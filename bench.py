@@ -9,9 +9,13 @@
 A "step" is one full optimisation step of ``UDAIICEpocher`` (one U-Net forward on LB+2*UB slices, supervised KL,
 UDA MSE, global+local IIC on three taps x five sub-heads, one backward, fused Adam) on synthetic ACDC-shaped
 1x256x256 4-class slices -- BASELINE.json configs[1]: LB=UB=16 per GPU, bf16 compute.  ``value`` = unique loader
-slices (LB+UB per rank) per second, whole job.  Rank 0 prints ONE JSON line with, besides the contract fields,
+slices (LB+UB per rank) per second, whole job.  Rank 0 prints ONE JSON line.  A plain run does only what that headline
+needs (set up, warm up, time the K steps); with ``--full`` the line also carries
   roofline     : the dominant kernel's algorithmic FLOP/s (HIP events on the launching stream, in the timed region)
+  kernel_ms_per_step_warmup, per_rank : the per-kernel table of the eager warm-up, each rank's host / all-reduce figures
   cpu_baseline : the CPU oracle (a port of the reference algorithm) timed on the host cores on a bounded sample.
+``--dump-outputs DIR`` writes what the last timed step handed its caller (the read-back losses and Dice counts, the updated
+model and projector state) as DIR/<name>.npy; the inputs depend only on the arguments, so two builds compare output for output.
 """
 import argparse
 import json
@@ -80,7 +84,7 @@ class StepDriver:
     """Runs UDAIICEpocher steps exactly as ``_run`` does (same code path, incl. the per-iteration meter read-back, which
     -- as in ``_run`` -- is taken after the next iteration is enqueued), but under external timing."""
 
-    def __init__(self, ep):
+    def __init__(self, ep, keep_last=False):
         from semi_seg._utils import FeatureExtractor
         from semi_seg.epocher import _Pending
         self.ep = ep
@@ -89,6 +93,14 @@ class StepDriver:
         ep._pending = _Pending()
         self._fx = FeatureExtractor(ep._model, ep._feature_position)
         ep._fextractor = self._fx.__enter__()
+        self.last = None
+        if keep_last:   # the most recent iteration's read-back (host scalars, Dice counts) as the epocher records it
+            record = ep._record
+
+            def keep(host, inter, union, label_group):
+                self.last = (host, inter, union)
+                record(host, inter, union, label_group)
+            ep._record = keep
 
     def step(self):
         ep = self.ep
@@ -97,6 +109,40 @@ class StepDriver:
     def close(self):
         self.ep._flush_records()
         self._fx.__exit__(None, None, None)
+
+
+DUMP_LIMIT = 64 << 20   # bytes, all files of one --dump-outputs together
+
+
+def write_outputs(out_dir, arrays):
+    """{name: tensor or host values} -> out_dir/<name>.npy: tensors as float32 (float64 if they are, and for integer / bool data),
+    host values as float64."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu()
+            out[name] = (a.double() if a.dtype == torch.float64 or not a.is_floating_point() else a.float()).numpy()
+        else:
+            out[name] = np.asarray(a, dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs would write {total} bytes (limit {DUMP_LIMIT})"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return len(out), total
+
+
+def step_outputs(drv):
+    """What the last timed step returned to its caller: the read-back losses (sup_loss, reg_loss, uda, mi and one mi per tap), the
+    Dice intersection / union counts, and the model and projector state the optimiser step left behind."""
+    ep = drv.ep
+    host, inter, union = drv.last
+    arrays = {"loss." + k.replace("/", "."): [v] for k, v in host.items() if isinstance(v, (int, float))}
+    arrays.update({"dice.inter": inter, "dice.union": union})
+    arrays.update({"model." + k: v for k, v in ep._model.state_dict().items()})
+    arrays.update({"projectors." + k: v for k, v in ep._projectors_wrapper.state_dict().items()})
+    return arrays
 
 
 def cpu_baseline(threads):
@@ -237,7 +283,19 @@ def input_pipeline_bench(args):
                          "peak": 8000.0, "unit": "GB/s", "frac": round(bytes_per_launch / (kern_ms * 1e-3) / 1e9 / 8000.0, 4),
                          "traffic": None, "avg_ms": round(kern_ms, 4), "launches_per_step": 2,
                          "note": "latency-bound: 32 blocks on 256 CUs; the host parameter draw dominates the step"}}
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.dump_outputs:
+        arrays = {}
+
+        def walk(x, name):
+            if isinstance(x, torch.Tensor):
+                arrays[name] = x
+            elif isinstance(x, (list, tuple)):
+                for i, y in enumerate(x):
+                    walk(y, f"{name}.{i}")
+        walk(keep[0], "labeled")        # the last batches the loaders handed out: [[image, label] per view], ...
+        walk(keep[1], "unlabeled")
+        write_outputs(args.dump_outputs, arrays)
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         from oracle import augment as OA
         rng = np.random.default_rng(0)
         img, gt = rng.integers(0, 256, (256, 256), dtype=np.uint8), rng.integers(0, 4, (256, 256), dtype=np.uint8)
@@ -312,8 +370,14 @@ def main():
     ap.add_argument("--mi-precision", default=None, choices=["fp32", "bf16x3", "f16f8", "bf16"],
                     help="local-MI contraction arithmetic (default: f16f8 with --dtype bfloat16 / float16 -- f16 hi x hi + fp8 cross terms "
                          "where a kernel has that form, the bf16 hi/lo split elsewhere -- and fp32 with --dtype float32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure what it does not need: the dominant kernel's roofline and the warm-up's per-kernel "
+                         "table (HIP events), each rank's host / all-reduce figures (per_rank) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="with --full: leave out the HIP-event kernel timing (roofline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (read-back losses and Dice counts, updated model and "
+                         "projector state; --workload input: the last batches) as DIR/<name>.npy, float32 / float64, 64 MB at most")
     ap.add_argument("--eager", action="store_true",
                     help="issue every iteration from Python (two threads, ~300 ctypes calls); default on one GPU: after three eager "
                          "iterations the library records its own calls during one more and replays that launch tape from one C call "
@@ -358,7 +422,7 @@ def main():
         if args.size == 256:
             args.size = 512
     ep, opt = build_step(device, args.lb, args.ub, args.size, args.dtype, rank, args.data, classes, patch)
-    drv = StepDriver(ep)
+    drv = StepDriver(ep, keep_last=bool(args.dump_outputs) and rank == 0)
     if distributed:
         opt.flat.ensure()
         ep._reducer = ddp.GradReducer(opt.flat, num_buckets=3)
@@ -383,7 +447,7 @@ def main():
         ep._TAPE_DEFAULT = False
     eager_warm = min(3, args.warmup) if use_tape else args.warmup
     survey, timer = None, None
-    use_timer = rank == 0 and not args.no_kernel_timer
+    use_timer = rank == 0 and args.full and not args.no_kernel_timer
     survey_steps = min(2, eager_warm) if use_timer else 0
     for i in range(args.warmup):
         if use_timer and i == eager_warm - survey_steps:
@@ -405,7 +469,7 @@ def main():
         table = sorted(survey.summary().items(), key=lambda kv: -kv[1]["min_ms"] * kv[1]["calls"])
         timer = _cabi.KernelTimer(only={table[0][0]})      # eager iterations of the timed region (all of them with --eager)
         _cabi.TIMER = timer
-    if distributed and getattr(ep, "_reducer", None) is not None:
+    if args.full and distributed and getattr(ep, "_reducer", None) is not None:
         ep._reducer.timing = True
         ep._reducer._wait_events = []
     # how long the host is BLOCKED per step (the one wait of an iteration: the previous iteration's scalars, _Pending.wait): the loop
@@ -419,7 +483,8 @@ def main():
         out = real_wait(ticket)
         blocked[0] += time.perf_counter() - tb
         return out
-    _Pending.wait = staticmethod(timed_wait)
+    if args.full:
+        _Pending.wait = staticmethod(timed_wait)
     barrier()
     tape = ep._step_tape
     if tape is not None and tape.handle and table:
@@ -444,11 +509,14 @@ def main():
         ex = ep._reducer.exposed_ms()
         mine["allreduce_exposed_ms_per_step"] = None if ex is None else round(ex, 4)
     per_rank = [mine]
-    if distributed:
+    if args.full and distributed:
         per_rank = [None] * world
         torch.distributed.all_gather_object(per_rank, mine)
     _cabi.TIMER = None
     drv.close()
+    if args.dump_outputs and rank == 0:
+        n, nbytes = write_outputs(args.dump_outputs, step_outputs(drv))
+        note(f"wrote {n} arrays ({nbytes / 2**20:.1f} MB) of the last timed step to {args.dump_outputs}")
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     if distributed:
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
@@ -476,8 +544,9 @@ def main():
             # what the collective library actually saw (1 / null when this is a single process without torch.distributed)
             "rccl_ranks": torch.distributed.get_world_size() if distributed else 1,
             "backend": torch.distributed.get_backend() if distributed else None,
-            "per_rank": per_rank,
         }
+        if args.full:
+            out["per_rank"] = per_rank
         if table:
             name, top = table[0]
             ms = [v for op in timed_ops for v in tape.timed_ms(op)] if timed_ops else []
@@ -511,7 +580,7 @@ def main():
                 out["roofline"]["issued_TFLOPs"] = round(tf / cf, 1) if cf else None
                 out["roofline"]["microbench_sustained_TFLOPs"] = MICROBENCH_SUSTAINED.get(mi_prec if name.startswith("iic_local") else "bf16")
             out["kernel_ms_per_step_warmup"] = {k: round(v["total_ms"] / survey_steps, 3) for k, v in table[:int(os.environ.get("MISEG_BENCH_TOP", "10"))]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cores = len(os.sched_getaffinity(0))
             except AttributeError:

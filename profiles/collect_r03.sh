@@ -6,11 +6,11 @@
 set -e
 R=$GRAFT_REPO_ROOT; T=${1:-r03a}; O=$R/gpurun_out/prof_$T; mkdir -p $O
 cd $R
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cp $O/bench_default.json $R/profiles/${T}_bench_default.json
 echo "default bench done: $(python3 -c "import json;d=json.load(open('$O/bench_default.json'));print(d['ms_per_step'], d['value'], d['roofline']['kernel'], d['roofline']['avg_ms'], d['roofline']['frac'])")"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o $T -- python3 $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline > $O/bench_profiled.log 2> $O/bench_profiled.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o $T -- python3 $R/bench.py --full --steps 5 --warmup 3 --no-cpu-baseline > $O/bench_profiled.log 2> $O/bench_profiled.err
 cd $R
 S=$(find $O -name "${T}_kernel_stats.csv" | head -1); K=$(find $O -name "${T}_kernel_trace.csv" | head -1)
 cp $S $R/profiles/${T}_bench_bf16_kernel_stats.csv

@@ -446,3 +446,21 @@ def test_bigstep_oracle_cache_is_current():
         names = [str(n) for n in z[f"{key}/scalar_names"]]
         assert {"sup_loss", "uda", "mi", "reg_loss", "mi/Up_conv2"} <= set(names), (key, names)
         assert len(z[f"{key}/grad_names"]) >= 8
+
+
+def test_bench_output_dump_types_and_limit(tmp_path):
+    """bench.py --dump-outputs: tensors of every storage type land as float32 (float64 when they are, and for integer data), host
+    scalars as float64, named DIR/<name>.npy; more than 64 MB in all is refused before anything is written."""
+    import bench
+    arrays = {"a": torch.arange(6, dtype=torch.bfloat16).reshape(2, 3), "b": torch.ones(3, dtype=torch.float16),
+              "c": torch.tensor([1.5], dtype=torch.float64), "d": torch.tensor([3, 4], dtype=torch.int64), "loss.x": [0.25]}
+    n, nbytes = bench.write_outputs(str(tmp_path / "o"), arrays)
+    got = {f[:-4]: np.load(tmp_path / "o" / f) for f in os.listdir(tmp_path / "o")}
+    assert n == 5 and set(got) == set(arrays)
+    assert got["a"].dtype == np.float32 and got["a"].tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert got["b"].dtype == np.float32 and got["c"].dtype == np.float64 and got["d"].dtype == np.float64 and got["d"].tolist() == [3, 4]
+    assert got["loss.x"].dtype == np.float64 and got["loss.x"].tolist() == [0.25]
+    assert nbytes == sum(a.nbytes for a in got.values())
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / "big"), {"w": torch.zeros(16 << 20 | 1)})
+    assert not (tmp_path / "big").exists()

@@ -158,11 +158,11 @@ def test_run_directory_matches_the_reference_trainers(golden, tmp_path, name):
 
 
 def test_bench_line_contract():
-    """`python bench.py` prints ONE JSON line with the driver's fields (metric / value / unit / n_gpus / steps / warmup / ms_per_step /
+    """`python bench.py --full` prints ONE JSON line with the driver's fields (metric / value / unit / n_gpus / steps / warmup / ms_per_step /
     higher_is_better / scaling / vs_baseline / dtype / data / config.workload), the `roofline` object of the dominant kernel measured
     with HIP events inside the timed region, and -- through `--gpus 1 --spawn`-style self-launch -- the rank count the process group saw."""
     import json
-    res = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"], cwd=ROOT, capture_output=True,
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"], cwd=ROOT, capture_output=True,
                          text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -179,3 +179,42 @@ def test_bench_line_contract():
         assert k in r, k
     assert r["bound"] == "mfma" and r["kernel"].startswith("iic_local_bwd") and r["peak"] == 2500.0
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3 and 0.05 < r["frac"] < 0.5 and r["avg_ms"] < d["ms_per_step"]
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) prints the headline fields only -- no roofline, per-kernel table, per-rank figures or
+    CPU baseline -- and `--dump-outputs DIR` writes what the last timed step handed back: its losses, Dice counts and the updated
+    model and projector state, every array float32 / float64."""
+    import json
+
+    import numpy as np
+    import torch
+    from contrastyou.arch import UNet
+    out_dir = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "4", "--lb", "2", "--ub", "2", "--size", "64",
+                          "--dump-outputs", str(out_dir)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert k in d, k
+    for k in ("roofline", "cpu_baseline", "per_rank", "kernel_ms_per_step_warmup"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 4 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 4 * 3 / (d["ms_per_step"] * 3e-3)) < 0.02 * d["value"]
+    files = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)}
+    assert all(f.endswith(".npy") for f in os.listdir(out_dir))
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum((out_dir / f).stat().st_size for f in os.listdir(out_dir)) <= 64 << 20
+    for k in ("loss.sup_loss", "loss.reg_loss", "loss.uda", "loss.mi", "dice.inter", "dice.union"):
+        assert k in files and np.isfinite(files[k]).all(), k
+    assert files["loss.sup_loss"].shape == (1,) and files["loss.sup_loss"][0] > 0
+    sd = UNet(input_dim=1, num_classes=4).state_dict()
+    assert {k for k in files if k.startswith("model.")} == {"model." + k for k in sd}
+    for k, v in sd.items():
+        assert files["model." + k].shape == tuple(v.shape), k
+    assert len([k for k in files if k.startswith("projectors.")]) > 0
+    w0 = files["model.DeConv_1x1.weight"]
+    torch.manual_seed(0)
+    assert np.isfinite(w0).all() and not np.array_equal(w0, UNet(input_dim=1, num_classes=4).state_dict()["DeConv_1x1.weight"].numpy())

@@ -459,12 +459,12 @@ def test_fp16_dynamic_loss_scale_under_the_tape():
 
 
 def test_bench_line_contract():
-    """`python bench.py` prints ONE JSON line with the driver's fields, the roofline object of the dominant kernel and the CPU
+    """`python bench.py --full` prints ONE JSON line with the driver's fields, the roofline object of the dominant kernel and the CPU
     baseline object (small shape here; the default invocation is the BASELINE configuration)."""
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "2", "--lb", "2", "--ub", "2", "--size", "64"],
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "2", "--lb", "2", "--ub", "2", "--size", "64"],
                          cwd=root, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
