@@ -323,6 +323,10 @@ int miseg_cat_flip(void* stream, const void* a, int64_t Na, const void* b, int64
  * rounded to dt_pad (MISEG_BF16 / MISEG_F16), channels 1..7 zero -- what miseg_cast_pad would make of `out` (unet.py:15, Conv1's input). */
 int miseg_cat_flip_pad(void* stream, const float* a, int64_t Na, const float* b, int64_t Nb, int64_t H, int64_t W,
                        const int32_t* flips, float* out, int dt_pad, void* pad8);
+/* out = [a | flip(b)] (Na + Nb samples, same element rules as miseg_cat_flip): the Mean Teacher student's input batch
+ * (ref contrastyou/epocher/base_epocher.py:176-181), whose teacher reads b unflipped. */
+int miseg_cat_flipped(void* stream, const void* a, int64_t Na, const void* b, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                      const int32_t* flips, void* out);
 /* argmax over channels + per-sample per-class intersection/union counts (int64 [N][C] each);
  * ref semi_seg/epocher.py:183 + whl:.../general_dice_meter.py:141-172. pred (int64 [N,H,W]) optional. */
 int miseg_argmax_dice(void* stream, const float* logits, const int64_t* labels, int64_t N, int64_t H, int64_t W,
@@ -549,6 +553,14 @@ int miseg_adam_step_scaled(void* stream, float* param, const float* grad, float*
 int miseg_adam_step_guarded(void* stream, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                             int64_t numel, float beta1, float beta2, const float* hyper, float grad_scale,
                             const float* guard, int64_t nguard);
+/* Mean Teacher EMA on flat fp32 buffers laid out alike   ref: whl:deepclustering2/models/ema.py:107-131
+ * teacher[i] = (teacher[i] * coef[0] + coef[1] * student[i]) * coef[2], coef = device fp32[3] (alpha, 1 - alpha, 1 - weight_decay) --
+ * the iteration's step block, so a replayed launch tape reads each step's alpha.  Rounded as torch's eager
+ * t.mul_(alpha).add_(s, alpha=1 - alpha).mul_(1 - wd) on the device (the add is one fused multiply-add), i.e. bit-equal to it.
+ * guard / nguard: the flags of miseg_adam_step_guarded; any non-zero or NaN one leaves the teacher untouched.  Both buffers
+ * 16-byte aligned. */
+int miseg_ema_update(void* stream, float* teacher, const float* student, int64_t numel, const float* coef,
+                     const float* guard, int64_t nguard);
 /* Overflow test of the half-precision modes (BASELINE configs[4]: torch.cuda.amp-style loss scaling; the reference itself trains in
  * fp32 and has no such step): count[0] = number of non-finite entries of grad[0..numel), as a float (0 = clean).  The caller appends
  * it to the guard flags of miseg_adam_step_guarded -- an overflowed gradient then moves neither parameters nor moments -- and the

@@ -433,6 +433,38 @@ extern "C" int miseg_cat_flip(void* stream, const void* a, int64_t Na, const voi
     return MISEG_OK;
 }
 
+// out = [a | flip(b)] along the batch dimension: the Mean Teacher student's input batch (ref contrastyou/epocher/base_epocher.py:176-181:
+// per-sample flips of the unlabeled images, then torch.cat behind the labeled ones).  The teacher reads b itself, unflipped.
+namespace miseg {
+__global__ __launch_bounds__(256) void cat_flipped_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out,
+                                                         int Na, int Nb, int C, int H, int W, const int32_t* __restrict__ flips) {
+    const int64_t per = (int64_t)C * H * W, total = (int64_t)(Na + Nb) * per;
+    for (int64_t e = blockIdx.x * 256LL + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t n = e / per, r = e - n * per;
+        uint32_t v;
+        if (n < Na) v = a[e];
+        else {
+            const int m = (int)(n - Na), f = flips[m];
+            const int w = r % W, h = (r / W) % H, c = r / ((int64_t)W * H);
+            const int hs = (f & 1) ? H - 1 - h : h, wsrc = (f & 2) ? W - 1 - w : w;
+            v = b[(int64_t)m * per + ((int64_t)c * H + hs) * W + wsrc];
+        }
+        out[e] = v;
+    }
+}
+}  // namespace miseg
+
+extern "C" int miseg_cat_flipped(void* stream, const void* a, int64_t Na, const void* b, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                                 const int32_t* flips, void* out) {
+    MISEG_TAPE(miseg_cat_flipped, stream, a, Na, b, Nb, C, H, W, flips, out);
+    MISEG_REQUIRE(out && flips && (a || Na == 0) && b && Na >= 0 && Nb > 0 && C > 0 && H > 0 && W > 0, "cat_flipped: bad args");
+    const int64_t total = (Na + Nb) * C * H * W;
+    hipLaunchKernelGGL(cat_flipped_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 8192)), dim3(256), 0, as_stream(stream),
+                       (const uint32_t*)a, (const uint32_t*)b, (uint32_t*)out, (int)Na, (int)Nb, (int)C, (int)H, (int)W, flips);
+    MISEG_LAUNCH_CHECK("cat_flipped_kernel");
+    return MISEG_OK;
+}
+
 extern "C" int miseg_argmax_dice(void* stream, const float* logits, const int64_t* labels, int64_t N, int64_t H, int64_t W, int64_t C,
                                  int64_t* pred, int64_t* inter, int64_t* uni) {
     MISEG_TAPE(miseg_argmax_dice, stream, logits, labels, N, H, W, C, pred, inter, uni);

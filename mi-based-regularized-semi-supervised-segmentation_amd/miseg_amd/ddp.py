@@ -206,4 +206,10 @@ def attach(trainer, num_buckets: int = 3) -> Optional[GradReducer]:
         raise RuntimeError("data-parallel training needs the flat-buffer FusedAdam (Optim.name: Adam)")
     trainer.to(trainer._device)
     trainer._grad_reducer = GradReducer(optimizer.flat, num_buckets=num_buckets)
+    teacher, updater = getattr(trainer, "_teacher_model", None), getattr(trainer, "_ema_updater", None)
+    if teacher is not None and updater is not None:
+        # Mean Teacher: rank 0's teacher everywhere (its flat mirror of the student's buffer: one broadcast).  The student is identical
+        # on every rank after each all-reduce, so the EMA keeps the teachers identical with no communication; the teacher's BatchNorm
+        # buffers stay rank-local like the student's.
+        dist.broadcast(updater.flats(teacher, optimizer.flat).flat_param, src=0)
     return trainer._grad_reducer

@@ -11,6 +11,7 @@ are re-pointed into ONE contiguous fp32 buffer, their ``.grad`` into a second on
 from __future__ import annotations
 
 import math
+import weakref
 from typing import Dict, Iterable, List, Optional
 
 import torch
@@ -18,6 +19,17 @@ from torch import Tensor
 
 from . import unet_ops
 from .gradslot import grad_slot  # noqa: F401  (re-exported)
+
+
+OWNERS: "weakref.WeakValueDictionary[int, FlatBuffers]" = weakref.WeakValueDictionary()   # id(first given parameter) -> its buffers
+
+
+def owner_of(params: List[torch.nn.Parameter]) -> Optional["FlatBuffers"]:
+    """The live flat buffers built for exactly ``params`` (in that order), if any."""
+    fb = OWNERS.get(id(params[0])) if params else None
+    if fb is None or len(fb.given) != len(params) or any(a is not b for a, b in zip(fb.given, params)) or not fb.valid():
+        return None
+    return fb
 
 
 class FlatBuffers:
@@ -30,6 +42,7 @@ class FlatBuffers:
 
     def __init__(self, params: List[torch.nn.Parameter]):
         self.params = params
+        self.given = list(params)     # the caller's order (MirrorBuffers maps a second network onto the layout by position)
         self.flat_param: Optional[Tensor] = None
         self.flat_grad: Optional[Tensor] = None
         self.offsets: List[int] = []
@@ -70,6 +83,7 @@ class FlatBuffers:
                 p._miseg_grad_claimed = True   # slots open at zero_grad()
                 self.slots.append(gview)
         self._offset_by_id = {id(p): o for p, o in zip(self.params, self.offsets)}
+        OWNERS[id(self.given[0])] = self
         self.flat_param, self.flat_grad = flat_p, flat_g
         unet_ops.PACK_CACHE.invalidate()
 
@@ -139,6 +153,58 @@ class FlatBuffers:
                 p.grad = slot
 
 
+class MirrorBuffers:
+    """One flat fp32 buffer for the parameters of a second network that follows ``like``'s layout exactly: same order, same
+    offsets, same 16-byte padding (a Mean Teacher's teacher, whose parameters are an exponential moving average of the student's --
+    the whole update is then ONE elementwise launch over the two buffers, ``unet_ops.ema_update``).  No gradient buffer: the
+    mirrored network is never trained.  Its conv weights are cached by ``unet_ops.PACK_CACHE`` like the optimiser's (``_miseg_mirror``),
+    so they are re-packed in the same single launch as the student's."""
+
+    def __init__(self, params: List[torch.nn.Parameter], like: FlatBuffers):
+        self.params = list(params)
+        self.like = like
+        self.flat_param: Optional[Tensor] = None
+        self.offsets: List[int] = []
+
+    def valid(self) -> bool:
+        return self.flat_param is not None and self.like.valid() and self.flat_param.numel() == self.like.total and \
+            all(p.data_ptr() == self.flat_param.data_ptr() + 4 * o for p, o in ((self.params[0], self.offsets[0]), (self.params[-1], self.offsets[-1])))
+
+    def build(self) -> None:
+        like = self.like
+        like.ensure()
+        # the student's layout order (FlatBuffers._layout_order) mapped onto this network by parameter position
+        position = {id(p): i for i, p in enumerate(like_params_in_model_order(like))}
+        mine = self.params
+        if len(mine) != len(like.params):
+            raise RuntimeError(f"mirror: {len(mine)} parameters against the flat buffer's {len(like.params)}")
+        ordered = [mine[position[id(q)]] for q in like.params]
+        dev = like.flat_param.device
+        flat = torch.zeros(like.total, dtype=torch.float32, device=dev)
+        offsets = []
+        with torch.no_grad():
+            for p, q, o in zip(ordered, like.params, like.offsets):
+                if p.shape != q.shape or p.dtype != torch.float32:
+                    raise RuntimeError(f"mirror: parameter {tuple(p.shape)} / {p.dtype} against {tuple(q.shape)} of the flat buffer")
+                view = flat[o:o + p.numel()].view_as(p)
+                view.copy_(p.data.to(dev))
+                p.data = view
+                p._miseg_mirror = True
+                offsets.append(o)
+        assert offsets == like.offsets
+        self.params, self.offsets, self.flat_param = ordered, offsets, flat
+        unet_ops.PACK_CACHE.invalidate()
+
+    def ensure(self) -> None:
+        if not self.valid():
+            self.build()
+
+
+def like_params_in_model_order(fb: FlatBuffers) -> List[torch.nn.Parameter]:
+    """The flat buffer's parameters in the order they were handed to it (before ``_layout_order`` grouped them)."""
+    return list(getattr(fb, "given", fb.params))
+
+
 class LossScaler:
     """Dynamic loss scale of the half-precision storage mode (BASELINE configs[4]), torch.cuda.amp.GradScaler's policy without its
     host synchronisation: the device counts the non-finite entries of the flat gradient (``miseg_count_nonfinite``), that count is
@@ -194,6 +260,7 @@ class FusedAdam(torch.optim.Optimizer):
         self.grad_scale = 1.0   # gradients arrive multiplied by this (loss scale of the fp16 mode); divided out in the kernel
         self.loss_scaler: Optional[LossScaler] = None      # set by the train epocher in the fp16 storage mode
         self.last_nonfinite: Optional[Tensor] = None       # device float[1] of the latest ``apply`` in that mode
+        self.last_guard: Optional[Tensor] = None           # device flags that guarded the latest ``apply`` (None: unguarded)
 
     @property
     def flat(self) -> FlatBuffers:
@@ -276,6 +343,7 @@ class FusedAdam(torch.optim.Optimizer):
                     guard = io.guard_with_overflow(guard, bad)
                     scale = -1.0                           # 1 / loss scale is hyper[4] of the step block
                 unet_ops.adam_step(fb.flat_param, fb.flat_grad, self._m[gi], self._v[gi], io.hyper(gi), b1, b2, scale, guard)
+            self.last_guard = guard         # the flags that guarded the update (a Mean Teacher's EMA launch reads the same ones)
             unet_ops.PACK_CACHE.invalidate()
             return
         for gi, group in enumerate(self.param_groups):
@@ -288,6 +356,7 @@ class FusedAdam(torch.optim.Optimizer):
                 self.last_nonfinite = bad if self.last_nonfinite is None else self.last_nonfinite + bad
                 guard = bad if guard is None else torch.cat([guard.reshape(-1), bad])
             unet_ops.adam_step(fb.flat_param, fb.flat_grad, self._m[gi], self._v[gi], self._hyper[gi], b1, b2, self.grad_scale, guard)
+        self.last_guard = guard
         unet_ops.PACK_CACHE.invalidate()   # the fp32 masters changed: packed operand copies are stale
 
     @torch.no_grad()

@@ -1077,3 +1077,16 @@ def cat_flip(a: Tensor, b: Tensor, flips: Tensor, stem_dtype=None) -> Tensor:
         return out
     call("miseg_cat_flip", _stream(), _ptr(a), na, _ptr(b), nb, a.shape[1], a.shape[2], a.shape[3], _ptr(flips), _ptr(out))
     return out
+
+
+def cat_flipped(a: Tensor, b: Tensor, flips: Tensor) -> Tensor:
+    """``torch.cat([a, flip(b)])`` along dim 0 in one launch: the Mean Teacher student's input batch (ref
+    contrastyou/epocher/base_epocher.py:176-181); the teacher reads ``b`` itself."""
+    _need_gpu(a, b, flips)
+    a, b = a.contiguous(), b.contiguous()
+    assert a.dtype == b.dtype and a.shape[1:] == b.shape[1:] and a.element_size() == 4 and a.dim() == 4, (a.shape, b.shape, a.dtype)
+    assert flips.dtype == torch.int32 and flips.numel() >= b.shape[0]
+    na, nb = a.shape[0], b.shape[0]
+    out = torch.empty((na + nb,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
+    call("miseg_cat_flipped", _stream(), _ptr(a), na, _ptr(b), nb, a.shape[1], a.shape[2], a.shape[3], _ptr(flips), _ptr(out))
+    return out

@@ -35,6 +35,11 @@ OUT_BYTES = 65536
 CURRENT: Optional["StepIO"] = None
 
 
+def block_bytes(forwards: int) -> int:
+    """Block size with accumulator room for ``forwards`` U-Net training forwards (one: the shipped layout, PARAM_BYTES)."""
+    return PARAM_BYTES + (int(forwards) - 1) * ACC_CAP * 8
+
+
 def current() -> Optional["StepIO"]:
     return CURRENT
 
@@ -49,11 +54,19 @@ class Ticket:
 
 
 class StepIO:
-    def __init__(self, device, slots: int = 4):
+    """``param_bytes``: size of the host -> device block; what lies beyond ``ACC_OFF`` is BatchNorm accumulator space.  The default
+    holds one U-Net training forward (at most 2 sum(C_out) + 2 x 22 = 3 468 of ACC_CAP = 4 096 words); an iteration with two
+    training forwards (Mean Teacher: student and teacher) sizes its block with ``block_bytes(2)``."""
+
+    def __init__(self, device, slots: int = 4, param_bytes: int = PARAM_BYTES):
         self.device = torch.device(device)
         lib = _cabi.lib()
-        self.dev = torch.zeros(PARAM_BYTES, dtype=torch.uint8, device=self.device)
-        self.host = torch.zeros(slots, PARAM_BYTES, dtype=torch.uint8).pin_memory()
+        if param_bytes < PARAM_BYTES or param_bytes % 16:
+            raise _cabi.MisegError(f"StepIO: a block of {param_bytes} bytes is smaller than the layout's {PARAM_BYTES}")
+        self.param_bytes = int(param_bytes)
+        self.acc_cap = (self.param_bytes - ACC_OFF) // 8
+        self.dev = torch.zeros(self.param_bytes, dtype=torch.uint8, device=self.device)
+        self.host = torch.zeros(slots, self.param_bytes, dtype=torch.uint8).pin_memory()
         self.up_events = [lib.miseg_event_create() for _ in range(slots)]
         self.up_pending = [False] * slots
         self.turn = 0
@@ -113,7 +126,7 @@ class StepIO:
         """The one host -> device copy of the iteration (current stream) and the event that frees the slot."""
         from .ops import _stream
         st = _stream()
-        call("miseg_upload", st, self.dev.data_ptr(), self.host[slot].data_ptr(), PARAM_BYTES)
+        call("miseg_upload", st, self.dev.data_ptr(), self.host[slot].data_ptr(), self.param_bytes)
         call("miseg_event_record", st, self.up_events[slot])
         self.up_pending[slot] = True
 
@@ -139,7 +152,7 @@ class StepIO:
         """``n`` int64 device words that are zero at the start of the iteration (the upload wrote them): a fixed-point statistics
         accumulator of one BatchNorm layer.  None when the block has no room left (the caller zero-fills a tensor of its own)."""
         i = self._cursor_acc
-        if i + n > ACC_CAP:
+        if i + n > self.acc_cap:
             return None
         self._cursor_acc += n
         return self._d_i64[ACC_OFF // 8 + i:ACC_OFF // 8 + i + n]

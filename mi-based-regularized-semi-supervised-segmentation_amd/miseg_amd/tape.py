@@ -149,9 +149,13 @@ class StepTape:
     # ------------------------------------------------------------------ per iteration
     def _key(self, io, li: Tensor, lt: Tensor, ui: Tensor, n_masks: int):
         from . import ops, unet_ops
+        # the last four entries name persistent state the recorded pointers depend on -- the packed weights and their job table
+        # (PACK_CACHE.generation) among them: a change releases the tape and re-records it
         return (tuple(li.shape), tuple(lt.shape), tuple(ui.shape), li.dtype, lt.dtype, ui.dtype, li.is_contiguous(), lt.is_contiguous(),
                 ui.is_contiguous(), n_masks, ops._stream(), ops._mi_precision, id(io), unet_ops.PACK_CACHE.generation,
                 self.ep._model.training, self.ep._tape_signature(), id(getattr(self.ep, "_reducer", None)))
+
+    _PERSISTENT = 4
 
     def step(self, io, li: Tensor, lt: Tensor, ui: Tensor, flip_masks):
         ep = self.ep
@@ -161,14 +165,27 @@ class StepTape:
         if self.handle and key == self.key:
             return self._replay(io, li, lt, ui, flip_masks)
         if self.handle:
-            if key[-3:] != self.key[-3:]:   # the persistent state moved or the trainer changed: the recorded pointers are void
+            if key[-self._PERSISTENT:] != self.key[-self._PERSISTENT:]:   # the persistent state moved or the trainer changed: the recorded pointers are void
                 self.release()
                 self.seen = 0
             return ep._run_step(io, li, lt, ui, flip_masks)      # (another batch shape, e.g. a short last batch: eager, the tape stays)
         if self.seen < self.warmup or not (li.is_contiguous() and lt.is_contiguous() and ui.is_contiguous()):
             self.seen += 1
             return ep._run_step(io, li, lt, ui, flip_masks)
+        if self._settle():
+            key = self._key(io, li, lt, ui, len(flip_masks))
         return self._record(io, li, lt, ui, flip_masks, key)
+
+    @staticmethod
+    def _settle() -> bool:
+        """Before recording: collect unreachable objects (a network that is garbage already must not die while its weights sit in the
+        recorded pack job table) and rebuild that table now, outside the recording.  True if the packed-weight generation moved."""
+        import gc
+        from . import unet_ops
+        before = unet_ops.PACK_CACHE.generation
+        gc.collect()
+        unet_ops.PACK_CACHE.settle()
+        return unet_ops.PACK_CACHE.generation != before
 
     # ------------------------------------------------------------------ record
     def _record(self, io, li, lt, ui, flip_masks, key):
@@ -219,7 +236,7 @@ class StepTape:
             "li": bind("li", li.data_ptr(), li.numel() * li.element_size()),
             "lt": bind("lt", lt.data_ptr(), lt.numel() * lt.element_size()),
             "ui": bind("ui", ui.data_ptr(), ui.numel() * ui.element_size()),
-            "up": bind("up", io.host[io.turn].data_ptr(), stepio.PARAM_BYTES),
+            "up": bind("up", io.host[io.turn].data_ptr(), io.param_bytes),
             "up_ev": bind("up_ev", io.up_events[io.turn], 1),
             "out": bind("out", io.out_host[ticket.slot].data_ptr(), stepio.OUT_BYTES),
             "out_ev": bind("out_ev", io.out_events[ticket.slot], 1),

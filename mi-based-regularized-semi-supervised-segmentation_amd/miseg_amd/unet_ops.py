@@ -204,7 +204,11 @@ class _PackCache:
     only change when the optimiser (or anything else that bumps ``epoch`` / the tensor version) rewrites the masters.
     The first request after such a change re-packs every registered weight with ``miseg_pack_conv3x3_weights_multi``;
     the rest of the step are dictionary hits.  Only parameters that live in a flat buffer are cached (their storage is
-    stable); anything else (e.g. the zero-padded stem weight) is packed on the spot."""
+    stable: the optimiser's, or a Mean Teacher's mirror of it, ``flat.MirrorBuffers``); anything else is packed on the spot.
+
+    ``generation`` names the set of packed tensors and the device job table: a launch tape records both addresses, so the
+    generation moves whenever either changes -- a new entry, a registered weight that died (its weak reference's callback, so
+    that the very next step sees it, before anything is replayed), and every rebuild of the job table."""
 
     def __init__(self):
         self.epoch = 0            # bumped by FusedAdam.step / FlatBuffers.build / load_state_dict
@@ -217,16 +221,21 @@ class _PackCache:
     def invalidate(self) -> None:
         self.epoch += 1
 
+    def _died(self, _ref) -> None:
+        self.dirty = True
+        self.generation += 1
+
     def get(self, weight: Tensor, dtype, kind: int, cb: int, cs: int, cin: Optional[int] = None) -> Tensor:
         """``cin`` (forward layout only): input channels of the PACKED tensor when the weight has fewer (the stem); the kind word then
         carries the weight's own count in its high bits (miseg_pack_conv3x3_weights)."""
-        if getattr(weight, "_miseg_grad_slot", None) is None or not weight.is_cuda or _NO_PACK_CACHE:
+        if (getattr(weight, "_miseg_grad_slot", None) is None and not getattr(weight, "_miseg_mirror", False)) or not weight.is_cuda \
+                or _NO_PACK_CACHE:
             return _pack_now(weight, dtype, kind, cb, cs, cin=cin)
         key = (weight.data_ptr(), tuple(weight.shape), dtype, kind, cb, cs)
         ent = self.entries.get(key)
         if ent is None or ent[0]() is not weight:
             # entry: [weakref(weight), dtype, kind, cb, cs, packed, version packed at, epoch packed at]
-            ent = self.entries[key] = [weakref.ref(weight), dtype, kind, cb, cs, _pack_now(weight, dtype, kind, cb, cs, cin=cin),
+            ent = self.entries[key] = [weakref.ref(weight, self._died), dtype, kind, cb, cs, _pack_now(weight, dtype, kind, cb, cs, cin=cin),
                                        weight._version, self.epoch]
             self.dirty = True
             self.generation += 1
@@ -238,7 +247,13 @@ class _PackCache:
             ent[6], ent[7] = weight._version, self.epoch
         return ent[5]
 
-    def _repack_all(self) -> None:
+    def settle(self) -> None:
+        """Drop the entries of weights that died and rebuild the job table if that (or a new entry) left it stale; no packing."""
+        if self.dirty or any(ent[0]() is None for ent in self.entries.values()):
+            self.packed_epoch = -1            # the next request packs everything (one launch, from the new table)
+            self._repack_all(launch=False)
+
+    def _repack_all(self, launch: bool = True) -> None:
         dead = [k for k, ent in self.entries.items() if ent[0]() is None]   # parameters that no longer exist
         for k in dead:
             del self.entries[k]
@@ -251,7 +266,7 @@ class _PackCache:
             self.packed_epoch = self.epoch
             return
         if dead or self.dirty:
-            self.jobs_dev = {}
+            self.jobs_dev = {}            # frees the old table: a tape that recorded its address must re-record (generation below)
             by_dtype = {}
             for ent in self.entries.values():
                 by_dtype.setdefault(ent[1], []).append(ent)
@@ -265,6 +280,9 @@ class _PackCache:
                 table = torch.frombuffer(blob, dtype=torch.uint8).clone().to(ents[0][5].device)
                 self.jobs_dev[dtype] = (table, len(ents), first, ents)
             self.dirty = False
+            self.generation += 1
+        if not launch:
+            return
         for dtype, (table, n, blocks, ents) in self.jobs_dev.items():
             live = [ent[0]() for ent in ents]          # strong references for the duration of the launch
             call("miseg_pack_conv3x3_weights_multi", _stream(), _DT[dtype], _ptr(table), n, blocks)
@@ -314,15 +332,17 @@ class _ConvBNReLU(torch.autograd.Function):
         acc = None
         if stem and training and (counter is not None or not _BN_ACC):
             stem, packed = False, _pack(weight, dtype, 0, cin=c0 + c1)       # (the stem kernel hands its statistics to the accumulator only)
-        if image is not None and not stem:                                  # the MFMA path after all: materialise the padded operand
-            call("miseg_cast_pad", _stream(), _ptr(image), n * h * w, 1, _DT[dtype], _ptr(x0), c0)
-            image = None
         if training and counter is None and _BN_ACC and (stem or query("miseg_conv3x3_fwd_acc_supported", _DT[dtype], c0 + c1, n, h, w, cout)):
             # the statistics leave the convolution as fixed-point atomic adds into one [2 C] accumulator that the step block's upload
             # zeroed; the apply kernel turns them into coefficients itself: no partial rows, no finalize launch
             io = stepio.current()
             # (inside an iteration whose block has no room left: the row-per-block path below; stand-alone use of the layer: a zero fill)
             acc = io.acc64(2 * cout + 2) if io is not None else torch.zeros(2 * cout + 2, dtype=torch.int64, device=dev)   # sums + misfit count
+            if stem and acc is None:        # no room left: the stem kernel has no statistics rows, the packed MFMA path has
+                stem, packed = False, _pack(weight, dtype, 0, cin=c0 + c1)
+        if image is not None and not stem:                                  # the MFMA path after all: materialise the padded operand
+            call("miseg_cast_pad", _stream(), _ptr(image), n * h * w, 1, _DT[dtype], _ptr(x0), c0)
+            image = None
         if training and acc is None:       # rows of the statistics matrix: one per block of the kernel that will serve this shape
             parts = query("miseg_conv3x3_stats_parts", _DT[dtype], c0 + c1, n, h, w) if counter is not None else \
                 query("miseg_conv3x3_fwd_parts", _DT[dtype], c0 + c1, n, h, w, cout)
@@ -719,3 +739,17 @@ def adam_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, 
     # grad_scale == -1: the kernel reads 1 / loss scale from hyper[4] (the step block: a dynamic scale under a replayed launch tape)
     call("miseg_adam_step_guarded", _stream(), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), float(beta1),
          float(beta2), _ptr(hyper), float(grad_scale), _ptr(guard), 0 if guard is None else guard.numel())
+
+
+def ema_update(teacher: Tensor, student: Tensor, coef: Tensor, guard: Optional[Tensor] = None) -> None:
+    """Mean Teacher EMA on flat fp32 buffers laid out alike: ``teacher = (teacher * a + b * student) * d`` with ``coef`` = device
+    fp32[3] (a, b, d) = (alpha, 1 - alpha, 1 - weight_decay), rounded as torch's eager ``mul_ / add_ / mul_`` (include/miseg_hip.h);
+    ``guard``: the fused Adam's flags -- any non-zero / NaN one leaves the teacher untouched."""
+    _need_gpu(teacher, student, coef)
+    assert teacher.dtype == student.dtype == coef.dtype == torch.float32 and teacher.numel() == student.numel() and coef.numel() >= 3
+    assert teacher.is_contiguous() and student.is_contiguous() and coef.is_contiguous()
+    if guard is not None:
+        _need_gpu(guard)
+        assert guard.dtype == torch.float32 and guard.is_contiguous()
+    call("miseg_ema_update", _stream(), _ptr(teacher), _ptr(student), teacher.numel(), _ptr(coef), _ptr(guard),
+         0 if guard is None else guard.numel(), work=(0.0, 12.0 * teacher.numel()), tag="ema_update")

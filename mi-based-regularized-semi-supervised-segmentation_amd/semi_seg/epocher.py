@@ -303,6 +303,7 @@ class TrainEpocher(_num_class_mixin, _Epocher):
 
     _io = None
     _step_tape = None
+    _TRAIN_FORWARDS = 1       # U-Net training forwards per iteration: the step block's BatchNorm accumulator room (stepio.block_bytes)
     _TAPE_DEFAULT = os.environ.get("MISEG_TAPE", "1") != "0"
 
     def _io_for(self, device) -> "stepio.StepIO":
@@ -316,8 +317,11 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         io = self._io
         if io is None or io.device != torch.device(device):
             ctx = getattr(self._optimizer, "_miseg_step_ctx", None)
-            if ctx is None or ctx["io"].device != torch.device(device):
-                ctx = {"io": stepio.StepIO(device), "tape": None}
+            size = stepio.block_bytes(self._TRAIN_FORWARDS)
+            if ctx is None or ctx["io"].device != torch.device(device) or ctx["io"].param_bytes != size:
+                if ctx is not None and ctx["tape"] is not None:
+                    ctx["tape"].release()
+                ctx = {"io": stepio.StepIO(device, param_bytes=size), "tape": None}
                 try:
                     self._optimizer._miseg_step_ctx = ctx
                 except AttributeError:
@@ -458,6 +462,11 @@ class TrainEpocher(_num_class_mixin, _Epocher):
                 seed=seed, unlabeled_image=unlabeled_image, unlabeled_image_tf=unlabeled_image_tf,
                 unlabeled_logits=unlabel_logits, flips=flips, num_unlabeled=ub,
             )
+        return self._finish_step(sup_loss, reg_loss, label_logits, labels)
+
+    def _finish_step(self, sup_loss, reg_loss, label_logits: Tensor, labels: Tensor):
+        """The iteration's tail: the total loss, the forward read-back, backward, the guarded optimiser launch.  Returns the Dice
+        counts."""
         total_loss = sup_loss + self._reg_weight * reg_loss
         # Everything the read-back needs from the FORWARD pass is launched here, before backward: the Dice counts and the iteration's
         # report (meter values + the simplex / NaN flags that guard the update).  Issued after backward they sat behind the optimiser's
@@ -752,3 +761,101 @@ class UDAIICEpocher(IICTrainEpocher):
         # host-side bookkeeping lives here, not in regularization(): that one is part of the captured device step
         self.meters["iic_weight"].add(self._iic_weight)
         self.meters["uda_weight"].add(self._cons_weight)
+
+
+class MeanTeacherEpocher(TrainEpocher):
+    """Mean Teacher (ref contrastyou/epocher/base_epocher.py:129-216, trainer contrast_trainer.py:235-262): a student trained on
+    ``sup_loss + reg_weight * consistency(student(flip(u)), flip(teacher(u)))`` and a teacher that only runs forward and follows the
+    student as an exponential moving average (``deepclustering2.models.ema_updater``).  One iteration:
+
+    1. flip decisions of the unlabeled batch under ``FixRandomSeed(seed)`` (the ``semi_seg`` transformer, as the other epochers);
+    2. the teacher's forward (train mode, no autograd) on the UNFLIPPED unlabeled batch: its own batch statistics, its own running
+       statistics;
+    3. the student's forward on ``[labeled | flip(unlabeled)]`` (one launch assembles it, ``ops.cat_flipped``);
+    4. KL to the one-hot labels + ``reg_weight`` x the fused softmax-MSE (``name: kl``: the fused KL consistency) against the
+       teacher's logits, flipped inside the loss kernel;
+    5. backward, the guarded fused Adam on the student, then ONE ``miseg_ema_update`` launch over the teacher's flat buffer, guarded
+       by the same flags: a skipped iteration moves neither network (the call count still advances, as the reference's does).
+
+    The EMA's coefficients (alpha changes every step) ride in the step block, one row behind Adam's, so a replayed launch tape reads
+    them; the block has accumulator room for both training forwards."""
+
+    _TRAIN_FORWARDS = 2
+
+    def __init__(self, model, teacher_model, optimizer, labeled_loader: T_loader, unlabeled_loader: T_loader, sup_criterion: T_loss,
+                 reg_criterion: T_loss, reg_weight: float, num_batches: int, cur_epoch=0, device="cpu", feature_position=None,
+                 feature_importance=None, ema_updater=None) -> None:
+        super().__init__(model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_weight, num_batches, cur_epoch,
+                         device, feature_position, feature_importance)
+        assert ema_updater is not None, "the Mean Teacher needs an ema_updater"
+        self._teacher_model = teacher_model
+        self._reg_criterion = reg_criterion
+        self._ema_updater = ema_updater
+        self._ema_row = None
+
+    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
+        meters = super()._configure_meters(meters)
+        meters.register_meter("reg_weight", AverageValueMeter())
+        return meters
+
+    def _run(self, *args, **kwargs) -> EpochResultDict:
+        self._teacher_model.train()
+        self.meters["reg_weight"].add(self._reg_weight)
+        return super()._run(*args, **kwargs)
+
+    def _stage(self, io, flip_masks) -> int:
+        """Adam's rows, then the EMA's (alpha, 1 - alpha, 1 - weight decay) of this call as one more row of the block."""
+        if not hasattr(self._optimizer, "host_step"):
+            raise RuntimeError("Trainer.name=meanteacher needs the fused Adam (Optim.name: Adam)")
+        rows = self._optimizer.host_step()
+        scale = self._loss_scale()
+        self._optimizer.grad_scale = scale
+        self._ema_row = len(rows)
+        self._ema_updater.flats(self._teacher_model, self._optimizer.flat)     # the teacher's mirror of the student's flat buffer
+        return io.stage(flip_masks, list(rows) + [list(self._ema_updater.host_step()) + [0.0]], scale)
+
+    def _tape_signature(self):
+        m = self._ema_updater._mirror
+        buf = next(iter(self._teacher_model.buffers()), None)
+        u = self._ema_updater
+        return super()._tape_signature() + (id(self._teacher_model), None if m is None or m.flat_param is None else m.flat_param.data_ptr(),
+                                            None if buf is None else buf.data_ptr(), u._alpha, u._justify_alpha, u._weight_decay, u._update_bn)
+
+    def _device_step(self, labeled_image: Tensor, labeled_target: Tensor, unlabeled_image: Tensor, flips2: Tensor, seed: int = None):
+        lb, ub = len(labeled_image), len(unlabeled_image)
+        self._flips2 = flips2
+        flips = flips2[:ub]
+        if labeled_image.dtype == unlabeled_image.dtype == torch.float32 and labeled_image.dim() == 4 and \
+                labeled_image.shape[1:] == unlabeled_image.shape[1:] and labeled_image.is_cuda:
+            batch = ops.cat_flipped(labeled_image, unlabeled_image, flips)      # [labeled | flip(unlabeled)] (ref :176-181)
+        else:
+            batch = torch.cat([labeled_image, ops.flip(unlabeled_image, flips)], dim=0)
+        with checks.deferred(self._pending.checks):
+            with torch.no_grad():          # the teacher: train mode, its own batch statistics, no autograd (ref :187-188)
+                teacher_logits = self._teacher_model(unlabeled_image)
+            self._before_forward(ub)
+            try:
+                predict_logits = self._model(batch)
+            finally:
+                self._after_forward()
+        label_logits, unlabel_tf_logits = ops.split_rows(predict_logits, [lb, ub])
+        labels = labeled_target.squeeze(1)
+        with checks.deferred(self._pending.checks):
+            if isinstance(self._sup_criterion, KL_div) and self._sup_criterion.supports_fused():
+                sup_loss = self._sup_criterion.from_logits(label_logits, labels)
+            else:
+                sup_loss = self._sup_criterion(label_logits.softmax(1), class2one_hot(labels, self.num_classes))
+            reg_loss = self._consistency(unlabel_tf_logits, teacher_logits, flips)
+        inter, union = self._finish_step(sup_loss, reg_loss, label_logits, labels)
+        # the EMA after Adam (ref :205-206), guarded by the flags that guarded Adam
+        self._ema_updater.apply(self._teacher_model, self._optimizer.flat, stepio.CURRENT.hyper(self._ema_row)[:3],
+                                getattr(self._optimizer, "last_guard", None))
+        return inter, union
+
+    def _consistency(self, student_tf_logits: Tensor, teacher_logits: Tensor, flips: Tensor):
+        """``reg_criterion(softmax(student(flip(u))), softmax(flip(teacher(u))).detach())`` (ref :193-194)."""
+        if isinstance(self._reg_criterion, nn.MSELoss):
+            return LinearLoss.of(ops.softmax_mse(student_tf_logits, teacher_logits, flips))
+        if isinstance(self._reg_criterion, KL_div) and self._reg_criterion.supports_fused():
+            return LinearLoss.of(ops.softmax_kl_consistency(student_tf_logits, teacher_logits, flips))
+        return self._reg_criterion(student_tf_logits.softmax(1), ops.flip(teacher_logits, flips).softmax(1).detach())

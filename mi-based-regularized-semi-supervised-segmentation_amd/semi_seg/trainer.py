@@ -1,6 +1,6 @@
-"""The four semi-supervised trainers behind ``Trainer.name`` (ref ``semi_seg/trainer.py:24-214``).
+"""The semi-supervised trainers behind ``Trainer.name`` (ref ``semi_seg/trainer.py:24-214``).
 
-Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}``, the keyword-only constructor, ``init()``,
+Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT), the keyword-only constructor, ``init()``,
 ``start_training()``, ``inference(checkpoint)``, ``set_feature_positions`` and the attribute names the checkpoint tree is
 keyed by (``_model``, ``_optimizer``, ``_scheduler``, ``_projector_wrappers``, ``_IIDSegWrapper``, ``_storage`` ...; the
 tree itself is pinned by ``tests/golden/trainer_io.npz``).  Config sections are the ones of ``config/semi.yaml``.
@@ -157,12 +157,15 @@ class SemiTrainer(Trainer):
         self._storage.to_csv(self._save_dir)
 
     # ------------------------------------------------------------------ inference
+    def _inference_model(self) -> nn.Module:
+        return self._model
+
     def inference(self, checkpoint=None):  # noqa
         if checkpoint is not None and not Path(checkpoint).exists():
             raise AssertionError(checkpoint)         # the reference asserts the path (semi_seg/trainer.py:112-115) before resolving it
         target = _checkpoint_file(checkpoint, self._save_dir)
         self.load_state_dict_from_path(str(target), strict=True)
-        runner = E.InferenceEpocher(self._model, val_loader=self._test_loader, sup_criterion=self._sup_criterion,
+        runner = E.InferenceEpocher(self._inference_model(), val_loader=self._test_loader, sup_criterion=self._sup_criterion,
                                     cur_epoch=self._cur_epoch, device=self._device)
         runner.set_save_dir(self._save_dir)
         return runner.run()
@@ -218,4 +221,38 @@ class UDAIICTrainer(IICTrainer):
                                iic_weight=self._iic_weight, **self._epoch_args())
 
 
-trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer}
+class MeanTeacherTrainer(SemiTrainer):
+    """``meanteacher``: the baseline of the paper's comparisons (ref contrastyou/trainer/contrast_trainer.py:235-262).  The student
+    is trained with ``MeanTeacherParameters.weight`` x consistency (``name``: mse | kl) against a teacher -- a second ``UNet(**Arch)``
+    with its own initialisation and no gradients -- that follows the student as an exponential moving average
+    (``alpha``, ``weight_decay``; ``deepclustering2.models.ema_updater``).  Validation, test and ``inference`` evaluate the TEACHER
+    (ref :261), so the best checkpoint is the teacher's best.  Checkpoints carry ``_teacher_model`` and ``_ema_updater``."""
+
+    def _init(self) -> None:
+        super()._init()
+        from contrastyou.arch import UNet
+        from deepclustering2.models import ema_updater
+        section = self._config["MeanTeacherParameters"]
+        self._reg_criterion, self._reg_weight = _consistency_section(section)
+        self._teacher_model = UNet(**self._config["Arch"])
+        for param in self._teacher_model.parameters():
+            param.detach_()
+            param.requires_grad_(False)
+        self._teacher_model.train()
+        self._ema_updater = ema_updater(alpha=float(section["alpha"]), justify_alpha=True, weight_decay=float(section["weight_decay"]),
+                                        update_bn=False)
+
+    def _make_epocher(self):
+        return E.MeanTeacherEpocher(self._model, self._teacher_model, self._optimizer, self._labeled_loader, self._unlabeled_loader,
+                                    self._sup_criterion, reg_criterion=self._reg_criterion, reg_weight=self._reg_weight,
+                                    ema_updater=self._ema_updater, **self._epoch_args())
+
+    def _eval_epoch(self, *, loader: T_loader, **kwargs) -> Tuple[EpochResultDict, float]:
+        return E.EvalEpocher(self._teacher_model, val_loader=loader, sup_criterion=self._sup_criterion, cur_epoch=self._cur_epoch,
+                             device=self._device).run()
+
+    def _inference_model(self):
+        return self._teacher_model
+
+
+trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer, "meanteacher": MeanTeacherTrainer}
