@@ -148,6 +148,23 @@ int miseg_iic_local_bwd(void* stream, const float* x, const float* y, const floa
                         const float* grad_raw, const float* scale, float* gx, float* gy, int accumulate, int precision,
                         void* ws, int64_t ws_bytes);
 int64_t miseg_iic_local_bwd_ws_bytes(int64_t K, int64_t pad, int64_t P);
+/* The same local MI on the NETWORK OUTPUT (the `midl` trainer): x = softmax(flip(b)), y = softmax(a) computed
+ * in registers from fp32 NHWC logits a, b [N][H][W][C] (the rows miseg_softmax_mse reads; flips = its int32[N] mask applied to b),
+ * never written out.  2 <= C <= 8 and 0 <= pad <= 3; anything else returns MISEG_E_INVALID ("unsupported configuration"), and the
+ * ws query returns -1.  Windows as above; any list (clamped, overlapping, not covering the map).
+ * joint_fwd : raw[P][T][T][C][C] exactly as miseg_iic_local_joint_fwd writes it for (x, y) -- the loss and grad_raw then come from
+ *             miseg_iic_local_loss_fwd(_ws).  Deterministic (per-block partials in ws, added in a fixed order): repeated calls are
+ *             bit-identical.  ws: miseg_iic_out_joint_ws_bytes() bytes.
+ * bwd       : ga = d/da, gb = d/db of sum_p scale[p] * loss[p] (scale = fp32[P] DEVICE array, upstream grad / P), through the joint
+ *             with each window's zero padding, overlapping windows summed, the softmax backward and, for gb, the flip back.  Every
+ *             pixel of both is written once (zero where no window covers it); accumulate = 1: ga += instead (the tf half already holds
+ *             the consistency gradient).  No workspace. */
+int64_t miseg_iic_out_joint_ws_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t pad, int64_t P);
+int miseg_iic_out_joint_fwd(void* stream, const float* a, const float* b, const int32_t* flips, int64_t N, int64_t C, int64_t H,
+                            int64_t W, int64_t pad, const int32_t* win, int64_t P, float* raw, void* ws, int64_t ws_bytes);
+int miseg_iic_out_bwd(void* stream, const float* a, const float* b, const int32_t* flips, int64_t N, int64_t C, int64_t H, int64_t W,
+                      int64_t pad, const int32_t* win, int64_t P, const float* grad_raw, const float* scale, float* ga, float* gb,
+                      int accumulate);
 /* All S sub-heads of a tap in one launch (ref semi_seg/epocher.py:264-272 loops `criterion(p[:ub], p[ub:]) for p in probs`):
  * probs fp32 [S][2*UB][K][H][W], x_s = probs[s][:UB], y_s = probs[s][UB:]; raw [S][P][T][T][K][K]; grad_raw likewise;
  * scale [S][P]; gprob like probs.  Workspaces: max of the single-head queries evaluated at P*S and at P (shapes the

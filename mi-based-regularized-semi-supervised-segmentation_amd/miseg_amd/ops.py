@@ -910,6 +910,84 @@ def softmax_kl_consistency(a: Tensor, b: Tensor, flips: Optional[Tensor] = None)
     return _SoftmaxKLCons.apply(a, b, flips)
 
 
+def output_local_mi_supported(c: int, pad: int) -> bool:
+    """Whether ``output_local_mi`` has a fused kernel for ``c`` classes and this padding (2 <= c <= 8, 0 <= pad <= 3)."""
+    return int(_cabi.lib().miseg_iic_out_joint_ws_bytes(1, int(c), 1, 1, int(pad), 1)) >= 0
+
+
+class _OutputLocalMI(torch.autograd.Function):
+    """loss[P] of IIDSegmentationLoss over the P windows (ref contrastyou/losses/iic_loss.py:107-149, :152-189) on
+    x = softmax(flip(b)), y = softmax(a), straight from the logits: the joint kernel computes both softmaxes in registers, the local-MI
+    epilogue (``_local_loss``) turns the joint into the losses and d loss / d joint, the backward kernel goes from there to the logits
+    of both sides.  Neither side is detached.
+
+    Gradient hand-over (no add launch): when ``a`` is a part of a ``split_rows`` whose rows another loss kernel has already written --
+    the consistency term, whose node is created after this one and therefore runs first in backward -- the kernel adds this term's
+    gradient into those rows and the node returns no gradient for ``a``; ``b``'s gradient is written into its part's rows.  In any
+    other order or layout the node returns fresh tensors and autograd adds as usual."""
+
+    @staticmethod
+    def forward(ctx, a: Tensor, b: Tensor, flips: Optional[Tensor], pad: int, windows, lamda: float):
+        _need_gpu(a, b, flips)
+        raw_a, raw_b = a, b
+        a, b = _logits_nhwc(a), _logits_nhwc(b)
+        if a.shape != b.shape:
+            raise _cabi.MisegError(f"output_local_mi: logits {tuple(a.shape)} and {tuple(b.shape)} differ")
+        n, c, h, w = a.shape
+        if flips is not None and (flips.dtype != torch.int32 or flips.numel() < n):
+            raise _cabi.MisegError("output_local_mi: flips must be int32 with one mask per sample")
+        p, t, dev = len(windows), 2 * pad + 1, a.device
+        win = windows_tensor(windows, dev)
+        raw = torch.empty(p, t, t, c, c, dtype=torch.float32, device=dev)
+        ws = _ws(query("miseg_iic_out_joint_ws_bytes", n, c, h, w, pad, p), dev)
+        px = sum((a1 - a0) * (b1 - b0) for a0, a1, b0, b1 in windows)
+        call("miseg_iic_out_joint_fwd", _stream(), _ptr(a), _ptr(b), _ptr(flips), n, c, h, w, pad, _ptr(win), p, _ptr(raw), _ptr(ws),
+             ws.numel(), work=(2.0 * c * c * t * t * n * px, 2.0 * n * c * h * w * 4), tag=f"iic_out_joint_fwd[p{pad}]")
+        loss = scalar_out((p,), dev)
+        grad_raw = torch.empty_like(raw)
+        _local_loss(raw, c, pad, p, lamda, loss, grad_raw)
+        ctx.save_for_backward(a, b, flips, grad_raw, win)
+        ctx.pad = pad
+        ctx.parts = (_split_part_of(raw_a, a), _split_part_of(raw_b, b))
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss: Tensor):
+        if gloss is None:
+            return None, None, None, None, None, None
+        a, b, flips, grad_raw, win = ctx.saved_tensors
+        n, c, h, w = a.shape
+        part_a, part_b = ctx.parts
+        ga, gb, acc, ret_a, ret_b = None, None, 0, True, True
+        if part_a is not None and part_a[1] in part_a[0].filled:
+            cand = part_a[0].rows(part_a[1])
+            if cand.shape == a.shape and cand.stride() == a.stride():
+                ga, acc, ret_a = cand, 1, False              # += into the consistency gradient already there
+        if ga is None:
+            ga = empty_nhwc(n, c, h, w, torch.float32, a.device)
+        if part_b is not None and part_b[1] not in part_b[0].filled:
+            cand = part_b[0].rows(part_b[1])
+            if cand.shape == b.shape and cand.stride() == b.stride():
+                gb = cand
+                part_b[0].filled.add(part_b[1])
+        if gb is None:
+            gb = empty_nhwc(n, c, h, w, torch.float32, b.device)
+        t = 2 * ctx.pad + 1
+        call("miseg_iic_out_bwd", _stream(), _ptr(a), _ptr(b), _ptr(flips), n, c, h, w, ctx.pad, _ptr(win), win.shape[0], _ptr(grad_raw),
+             _ptr(gloss.contiguous().float()), _ptr(ga), _ptr(gb), acc,
+             work=(4.0 * c * c * t * t * n * h * w, n * c * h * w * 4.0 * (4 + acc)), tag=f"iic_out_bwd[p{ctx.pad}]")
+        return (ga if ret_a else None), (gb if ret_b else None), None, None, None, None
+
+
+def output_local_mi(a: Tensor, b: Tensor, flips: Optional[Tensor], pad: int, windows, lamda: float = 1.0) -> Tensor:
+    """loss[P] of ``IIDSegmentationSmallPathLoss(padding=pad)(softmax(flip(b)), softmax(a))`` per window (the reference averages them):
+    a, b = [N, C, H, W] logits (fp32 NHWC read in place; others converted), ``flips`` the per-sample masks of ``b``'s flip
+    (None: no flip), ``windows`` = [(h0, h1, w0, w1)] in the reference's patch order.  Only 2 <= C <= 8, 0 <= pad <= 3
+    (``output_local_mi_supported``); the library refuses anything else."""
+    return _OutputLocalMI.apply(a, b, flips, int(pad), [tuple(int(v) for v in w) for w in windows], float(lamda))
+
+
 def _flip_raw(x: Tensor, flips: Tensor) -> Tensor:
     _need_gpu(x, flips)
     if x.element_size() not in (2, 4, 8):
@@ -968,11 +1046,12 @@ class _SplitHolder:
     """Shared by the parts of one ``split_rows``: the batch gradient buffer that the split's backward returns.  A loss kernel whose
     input IS a part writes its scaled gradient straight into that part's rows (``_scaled_grad``: one launch, where autograd would
     multiply into a temporary and the split's backward would copy it over); the backward then only zero-fills the parts without a loss."""
-    __slots__ = ("meta", "sizes", "out")
+    __slots__ = ("meta", "sizes", "out", "filled")
 
     def __init__(self, x: Tensor, sizes):
         cl = x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
         self.meta, self.sizes, self.out = (tuple(x.shape), x.dtype, x.device, cl), list(sizes), None
+        self.filled = set()       # parts whose rows a loss kernel's backward has written in this backward pass
 
     def buffer(self) -> Tensor:
         if self.out is None:
@@ -1000,6 +1079,7 @@ def _scaled_grad(part, grad: Tensor, g: Tensor) -> Tensor:
         dst = holder.rows(idx)
         if dst.dtype == grad.dtype and dst.shape == grad.shape and dst.stride() == grad.stride():
             call("miseg_assemble_rows", _stream(), _ptr(dst), _ptr(grad), _ptr(g), grad.numel(), None, None, 0, None, None, 0)
+            holder.filled.add(idx)
             return dst
     return grad * g
 
@@ -1031,6 +1111,7 @@ class _SplitRows(torch.autograd.Function):
         holder = ctx.holder
         if holder is not None:
             out, holder.out = holder.buffer(), None
+            holder.filled = set()
         else:
             out = torch.empty(shape, dtype=dtype, device=device, memory_format=torch.channels_last if cl else torch.contiguous_format)
         o = 0

@@ -859,3 +859,67 @@ class MeanTeacherEpocher(TrainEpocher):
         if isinstance(self._reg_criterion, KL_div) and self._reg_criterion.supports_fused():
             return LinearLoss.of(ops.softmax_kl_consistency(student_tf_logits, teacher_logits, flips))
         return self._reg_criterion(student_tf_logits.softmax(1), ops.flip(teacher_logits, flips).softmax(1).detach())
+
+
+class MIDLTrainEpocher(UDATrainEpocher):
+    """``midl``: the UDA iteration (same flips, same ``[labeled | unlabeled | flip(unlabeled)]`` forward, same supervised KL) whose
+    regulariser adds the local mutual information of the network's OUTPUT (``MIDLPaperParameters``):
+
+        x = softmax(flip(unlabeled_logits)), y = softmax(unlabeled_tf_logits)               (the IIC tap's order, ref :249-275)
+        reg = cons_weight * UDA(y, x.detach()) + iic_weight * IIDSegmentationSmallPathLoss(padding, patch_size)(x, y)
+
+    with reg_weight 1 (as udaiic, ref trainer.py:187-196).  Neither side of the MI term is detached.  The MI term is one library
+    node (``ops.output_local_mi``: softmaxes in registers, the local-MI epilogue, a backward that ends on the logits and adds into
+    the consistency gradient's rows); shapes outside its envelope (more than 8 classes, padding above 3) run the reference's
+    composition -- torch softmax and this repo's generic ``IIDSegmentationSmallPathLoss`` -- eagerly: the launch tape then declines
+    with its usual warning.  Meters: the base ones, ``uda`` and ``mi`` (= -MI loss, the sign ``IICTrainEpocher`` reports)."""
+
+    def __init__(self, model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_criterion: T_loss, num_batches: int,
+                 cur_epoch: int = 0, device="cpu", feature_position=None, feature_importance=None, cons_weight: float = 5.0,
+                 iic_weight: float = 0.1, padding: int = 1, patch_size=1024) -> None:
+        super().__init__(model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_criterion, 1.0, num_batches, cur_epoch,
+                         device, feature_position, feature_importance)
+        from contrastyou.losses.iic_loss import IIDSegmentationSmallPathLoss
+        self._cons_weight, self._iic_weight = float(cons_weight), float(iic_weight)
+        self._mi_criterion = IIDSegmentationSmallPathLoss(lamda=1.0, padding=int(padding), patch_size=patch_size)
+
+    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
+        meters = super()._configure_meters(meters)
+        meters.register_meter("mi", AverageValueMeter())
+        return meters
+
+    def windows(self, h: int, w: int):
+        """The criterion's patches of an h x w map, (h0, h1, w0, w1) in the reference's order (patch_generator)."""
+        from contrastyou.losses.iic_loss import _windows
+        crit = self._mi_criterion
+        return _windows(h, w, crit._patch_size, crit._step_size)
+
+    def _mi(self, unlabeled_tf_logits: Tensor, unlabeled_logits: Tensor, flips: Tensor):
+        crit = self._mi_criterion
+        c, h, w = unlabeled_tf_logits.shape[1:]
+        if ops.output_local_mi_supported(c, crit.padding):
+            losses = ops.output_local_mi(unlabeled_tf_logits, unlabeled_logits, flips, crit.padding, self.windows(h, w), crit.lamda)
+            checks.raise_if_nan(losses, "midl: a patch loss of the output MI is nan")
+            return LinearLoss.mean(losses)
+        # out of the fused envelope: the reference's composition on the generic local-MI kernels (eager; the tape declines)
+        x = ops.flip(unlabeled_logits, flips).softmax(1)
+        y = unlabeled_tf_logits.float().softmax(1)
+        return crit(x.float(), y)
+
+    @_fused
+    def regularization(self, unlabeled_tf_logits: Tensor, unlabeled_logits_tf: Tensor = None, seed=None, *args,
+                       unlabeled_logits: Tensor = None, flips: Tensor = None, **kwargs):
+        # the MI node first: its backward then runs after the consistency term's and adds into the rows that one has written
+        mi_loss = self._mi(unlabeled_tf_logits, unlabeled_logits, flips)
+        cons_loss = self._uda(unlabeled_tf_logits, unlabeled_logits, flips)
+        self._pending.put("mi", -mi_loss)
+        return self._cons_weight * cons_loss + self._iic_weight * mi_loss
+
+    def _tape_signature(self):
+        crit = self._mi_criterion
+        return super()._tape_signature() + (self._iic_weight, crit.padding, crit.lamda, tuple(crit._patch_size), tuple(crit._step_size))
+
+    def _record(self, host, inter, union, label_group):
+        super()._record(host, inter, union, label_group)
+        if "mi" in host:
+            self.meters["mi"].add(host["mi"])

@@ -1,6 +1,7 @@
 """The semi-supervised trainers behind ``Trainer.name`` (ref ``semi_seg/trainer.py:24-214``).
 
-Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT), the keyword-only constructor, ``init()``,
+Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT, and ``midl``, the
+``MIDLPaperParameters`` section's trainer), the keyword-only constructor, ``init()``,
 ``start_training()``, ``inference(checkpoint)``, ``set_feature_positions`` and the attribute names the checkpoint tree is
 keyed by (``_model``, ``_optimizer``, ``_scheduler``, ``_projector_wrappers``, ``_IIDSegWrapper``, ``_storage`` ...; the
 tree itself is pinned by ``tests/golden/trainer_io.npz``).  Config sections are the ones of ``config/semi.yaml``.
@@ -255,4 +256,30 @@ class MeanTeacherTrainer(SemiTrainer):
         return self._teacher_model
 
 
-trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer, "meanteacher": MeanTeacherTrainer}
+class MIDLTrainer(UDATrainer):
+    """``midl``: ``UDARegCriterion.weight`` x consistency + ``MIDLPaperParameters.iic_weight`` x the local mutual information of the
+    network's output (``IIDSegmentationSmallPathLoss(padding, patch_size)`` on softmax(flip(f(x))) and softmax(f(flip(x)))); the
+    combined regulariser enters the loss with weight 1, as udaiic's.  No new modules: the checkpoint tree is the ``uda`` trainer's, and
+    validation, test and ``inference`` evaluate the model as for ``uda``.  Semantics: DESIGN.md section 12."""
+
+    def _init(self) -> None:
+        super()._init()
+        section = self._config["MIDLPaperParameters"]
+        self._uda_weight, self._reg_weight = self._reg_weight, 1.0
+        self._iic_weight = float(section["iic_weight"])
+        self._mi_padding, self._mi_patch_size = int(section["padding"]), int(section["patch_size"])
+
+    def mi_criterion(self):
+        """The MI term's criterion (the reference's class and its patch / step sizes); built where it is used, so that the trainer's
+        checkpoint tree stays the ``uda`` one."""
+        from contrastyou.losses.iic_loss import IIDSegmentationSmallPathLoss
+        return IIDSegmentationSmallPathLoss(lamda=1.0, padding=self._mi_padding, patch_size=self._mi_patch_size)
+
+    def _make_epocher(self):
+        return E.MIDLTrainEpocher(self._model, self._optimizer, self._labeled_loader, self._unlabeled_loader, self._sup_criterion,
+                                  self._reg_criterion, cons_weight=self._uda_weight, iic_weight=self._iic_weight,
+                                  padding=self._mi_padding, patch_size=self._mi_patch_size, **self._epoch_args())
+
+
+trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer, "meanteacher": MeanTeacherTrainer,
+                "midl": MIDLTrainer}

@@ -1,0 +1,429 @@
+"""GPU: the `midl` trainer (``Trainer.name=midl``) -- the fused output local-MI kernels against float64 autograd,
+peaked predictions, fused against the generic composition, the epocher against the reference's own run (tests/golden/midl.npz), the
+step under the launch tape, the out-of-envelope fallback and the CLI."""
+import json
+import os
+import random
+import shutil
+import subprocess
+import sys
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+import synth
+from oracle import iic as OI, unet as OU
+
+pytestmark = pytest.mark.gpu
+T = torch.from_numpy
+DEV = "cuda"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
+FEATURES = ["Conv5", "Up_conv3", "Up_conv2"]
+
+
+def _dump(tag, rows):
+    """With MISEG_ERROR_DUMP=<dir>, the achieved errors are written there as JSON (the numbers DESIGN.md section 12 quotes)."""
+    out = os.environ.get("MISEG_ERROR_DUMP")
+    if not out:
+        return
+    os.makedirs(out, exist_ok=True)
+    with open(os.path.join(out, f"midl_{tag}.json"), "w") as f:
+        json.dump(rows, f, indent=1)
+
+
+def _flip64(x, masks):
+    out = []
+    for v, m in zip(x, masks):
+        dims = [d for d, bit in ((1, 1), (2, 2)) if m & bit]
+        out.append(v.flip(dims) if dims else v)
+    return torch.stack(out)
+
+
+def _inputs(c, n, h, w, seed, scale=2.0, views=True):
+    """Logits a (the transformed view) and b (the untransformed one) with per-sample flip masks.  ``views``: a = flip(b) + noise, the
+    two views of one image as the trainer sees them (their MI is of order one); else independent (MI ~ 1e-3: there the loss is a
+    small difference of entropies and the shared fp32 epilogue's cancellation, not the joint, sets its relative error)."""
+    g = torch.Generator().manual_seed(seed)
+    b = torch.randn(n, c, h, w, generator=g) * scale
+    masks = [int(v) for v in torch.randint(0, 4, (n,), generator=g)]
+    noise = torch.randn(n, c, h, w, generator=g) * scale
+    a = _flip64(b, masks) + 0.5 * noise if views else noise
+    return a, b, masks
+
+
+def _reference(a, b, masks, pad, patch, cons=0.0):
+    """float64 autograd on CPU: mi = IIDSegmentationSmallPathLoss(pad, patch)(softmax(flip(b)), softmax(a)) (+ cons x MSE)."""
+    a64, b64 = a.double().requires_grad_(), b.double().requires_grad_()
+    x, y = _flip64(b64, masks).softmax(1), a64.softmax(1)
+    mi = OI.iid_seg_small_patch_loss(x, y, pad, patch)
+    total = mi + cons * ((y - x.detach()) ** 2).mean() if cons else mi
+    total.backward()
+    return float(mi.detach()), a64.grad, b64.grad
+
+
+def _windows(h, w, patch):
+    return OI.patch_windows(h, w, (patch, patch), (patch // 2, patch // 2))
+
+
+def _fused(a, b, masks, pad, patch, cons=0.0):
+    """The trainer's arrangement: a, b as parts of one NHWC logits batch [b | a] (split_rows), the MI node created first, the fused
+    consistency term second (its backward writes a's rows, the MI backward adds into them)."""
+    from miseg_amd import ops
+    from miseg_amd.lazy import LinearLoss
+    n = a.shape[0]
+    batch = torch.cat([b, a]).to(DEV).contiguous(memory_format=torch.channels_last).requires_grad_()
+    pb, pa = ops.split_rows(batch, [n, n])
+    flips = torch.tensor(masks, dtype=torch.int32, device=DEV)
+    losses = ops.output_local_mi(pa, pb, flips, pad, _windows(a.shape[2], a.shape[3], patch))
+    total = LinearLoss.mean(losses)
+    if cons:
+        total = total + cons * LinearLoss.of(ops.softmax_mse(pa, pb, flips))
+    total.backward()
+    mi = float(losses.detach().double().mean())
+    return mi, batch.grad[n:].cpu().double(), batch.grad[:n].cpu().double(), losses.detach().clone()
+
+
+def _rel(got, ref):
+    return float((got - ref).abs().max() / ref.abs().max())
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1. the kernels
+# Largest errors measured over the 18 cases of each kind, gradients relative to the largest entry; the bounds
+# below are at most 10x of them (the views' loss bound is the 1e-5 of the specification).
+#   views:       loss 7.8e-7, gradients 1.7e-5 (C = 8, pad 3, overlapping patches)
+#   independent: loss 3.5e-6, gradients 1.3e-5
+BOUNDS = {"views": (1e-5, 1e-4), "independent": (3e-5, 1e-4)}
+
+
+@pytest.mark.parametrize("kind", ["views", "independent"])
+@pytest.mark.parametrize("c", [2, 4, 8])
+@pytest.mark.parametrize("pad", [0, 1, 3])
+@pytest.mark.parametrize("patch", [1024, 16])
+def test_fused_loss_and_gradients_against_float64(c, pad, patch, kind):
+    """Odd 37 x 53 maps, random per-sample flips, the whole-map window (patch 1024) and 24 overlapping 16-pixel patches with clamped
+    last windows; the tf half already holds a consistency gradient the MI backward adds to."""
+    a, b, masks = _inputs(c, 3, 37, 53, seed=100 * c + 10 * pad + (patch == 16), views=kind == "views")
+    ref_mi, ref_ga, ref_gb = _reference(a, b, masks, pad, patch, cons=0.5)
+    mi, ga, gb, _ = _fused(a, b, masks, pad, patch, cons=0.5)
+    err = {"loss": abs(mi - ref_mi) / abs(ref_mi), "ga": _rel(ga, ref_ga), "gb": _rel(gb, ref_gb)}
+    _dump(f"kernel_{kind}_c{c}_p{pad}_patch{patch}", err)
+    loss_bound, grad_bound = BOUNDS[kind]
+    assert err["loss"] < loss_bound, err
+    assert err["ga"] < grad_bound and err["gb"] < grad_bound, err
+
+
+def test_fused_gradients_without_a_split_batch():
+    """Plain tensors (no split_rows, no consistency term): the node returns fresh gradients for both sides."""
+    from miseg_amd import ops
+    a, b, masks = _inputs(4, 2, 40, 33, seed=7)
+    ref_mi, ref_ga, ref_gb = _reference(a, b, masks, 2, 16)
+    ad = a.to(DEV).contiguous(memory_format=torch.channels_last).requires_grad_()
+    bd = b.to(DEV).contiguous(memory_format=torch.channels_last).requires_grad_()
+    flips = torch.tensor(masks, dtype=torch.int32, device=DEV)
+    losses = ops.output_local_mi(ad, bd, flips, 2, _windows(40, 33, 16))
+    losses.mean().backward()
+    err = {"loss": abs(float(losses.detach().double().mean()) - ref_mi) / abs(ref_mi), "ga": _rel(ad.grad.cpu().double(), ref_ga),
+           "gb": _rel(bd.grad.cpu().double(), ref_gb)}
+    _dump("kernel_nosplit", err)
+    assert err["loss"] < 1e-5 and err["ga"] < 8e-6 and err["gb"] < 8e-6, err        # measured 1.5e-7, 8.6e-7, 8.4e-7
+
+
+@pytest.mark.parametrize("c", [4, 8])
+def test_peaked_predictions(c):
+    """Logits scaled so that the predictions are nearly one-hot (the regime where the joint's min shift and the 1e-16 matter)."""
+    a, b, masks = _inputs(c, 2, 48, 48, seed=31 + c, scale=12.0)
+    for pad, patch in ((1, 1024), (3, 32)):
+        ref_mi, ref_ga, ref_gb = _reference(a, b, masks, pad, patch)
+        mi, ga, gb, _ = _fused(a, b, masks, pad, patch)
+        err = {"loss": abs(mi - ref_mi) / abs(ref_mi), "ga": _rel(ga, ref_ga), "gb": _rel(gb, ref_gb)}
+        _dump(f"peaked_c{c}_p{pad}", err)
+        assert err["loss"] < 1e-5, (pad, err)
+
+
+def test_fused_matches_the_generic_composition_and_repeats_bit_for_bit():
+    """torch softmax + this repo's generic IIDSegmentationSmallPathLoss (the fallback) against the fused node, fp32; two fused calls
+    are bit-identical (losses and gradients)."""
+    from contrastyou.losses.iic_loss import IIDSegmentationSmallPathLoss
+    from miseg_amd import ops
+    a, b, masks = _inputs(4, 3, 64, 64, seed=5)
+    for pad, patch in ((1, 1024), (3, 32)):
+        mi1, ga1, gb1, l1 = _fused(a, b, masks, pad, patch)
+        mi2, ga2, gb2, l2 = _fused(a, b, masks, pad, patch)
+        assert torch.equal(l1, l2) and torch.equal(ga1, ga2) and torch.equal(gb1, gb2)
+        ad = a.to(DEV).requires_grad_()
+        bd = b.to(DEV).requires_grad_()
+        flips = torch.tensor(masks, dtype=torch.int32, device=DEV)
+        crit = IIDSegmentationSmallPathLoss(padding=pad, patch_size=patch)
+        ops.set_mi_precision("fp32")
+        loss = crit(ops.flip(bd, flips).softmax(1), ad.softmax(1))
+        loss.backward()
+        err = {"loss": abs(float(loss) - mi1) / abs(mi1), "ga": _rel(ad.grad.cpu().double(), ga1), "gb": _rel(bd.grad.cpu().double(), gb1)}
+        _dump(f"composed_p{pad}", err)
+        assert err["loss"] < 1e-5 and err["ga"] < 2.5e-5 and err["gb"] < 2.5e-5, err      # measured <= 4.2e-7 and 3.1e-6
+
+
+def test_out_of_envelope_arguments_are_refused():
+    from miseg_amd import _cabi, ops
+    a = torch.randn(1, 12, 8, 8, device=DEV).contiguous(memory_format=torch.channels_last)
+    with pytest.raises(_cabi.MisegError):
+        ops.output_local_mi(a, a, None, 1, [(0, 8, 0, 8)])
+    a = a[:, :4].contiguous(memory_format=torch.channels_last)
+    with pytest.raises(_cabi.MisegError):
+        ops.output_local_mi(a, a, None, 5, [(0, 8, 0, 8)])
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2. the epocher
+def _unet(dtype, seed):
+    from contrastyou.arch import UNet
+    m = UNet(1, 4, compute_dtype=dtype)
+    m.load_state_dict(OU.init_state(1, 4, seed=seed))
+    return m.to(DEV)
+
+
+def _golden_run(g, geom, monkeypatch):
+    from deepclustering2.loss import KL_div
+    from deepclustering2.optim import Adam
+    from miseg_amd import ops, unet_ops
+    from semi_seg import epocher as E
+    cfg = {k[4:]: g[k].item() for k in g.files if k.startswith("cfg/")}
+    H, LB, UB, NB = int(cfg["H"]), int(cfg["LB"]), int(cfg["UB"]), int(cfg["NB"])
+    ops.set_mi_precision("fp32")
+    model = _unet("float32", int(cfg["model_seed"]))
+    opt = Adam(model.parameters(), lr=float(cfg["lr"]), weight_decay=float(cfg["wd"]))
+    lab = [(T(synth.uniform(f"midl/lab{i}", (LB, 1, H, H))), T(synth.integers(f"midl/tgt{i}", (LB, 1, H, H), 4))) for i in range(NB)]
+    unl = [T(synth.uniform(f"midl/unl{i}", (UB, 1, H, H))) for i in range(NB)]
+
+    def loader(imgs, tgts, B):
+        for img, tgt in zip(imgs, tgts):
+            yield [[[img, tgt], [img.clone(), tgt.clone()]], [f"patient{j:03d}_00_{j}" for j in range(B)], ["0"] * B,
+                   [f"patient{j:03d}_00" for j in range(B)]]
+
+    seeds = iter(int(s) for s in g[f"{geom}/seeds"])
+    monkeypatch.setattr(E.random, "randint", lambda a, b: next(seeds))
+    grads, per_step = [], []
+    real_adam = unet_ops.adam_step
+
+    def adam_spy(param, grad, *a, **k):
+        if not grads:
+            grads.append(grad.detach().clone())
+        return real_adam(param, grad, *a, **k)
+
+    monkeypatch.setattr(unet_ops, "adam_step", adam_spy)
+    ep = E.MIDLTrainEpocher(model, opt, loader([a for a, _ in lab], [b for _, b in lab], LB),
+                            loader(unl, [torch.zeros(UB, 1, H, H, dtype=torch.long)] * NB, UB), KL_div(verbose=False),
+                            torch.nn.MSELoss(), NB, 0, DEV, feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25],
+                            cons_weight=float(cfg["cons_weight"]), iic_weight=float(cfg["iic_weight"]),
+                            padding=int(g[f"{geom}/cfg/padding"]), patch_size=int(g[f"{geom}/cfg/patch_size"]))
+    ep._TAPE_DEFAULT = False
+    record = ep._record
+
+    def keep(host, *a):
+        per_step.append(dict(host))
+        record(host, *a)
+
+    ep._record = keep
+    res = ep.run()
+    monkeypatch.setattr(unet_ops, "adam_step", real_adam)
+    return res, grads[0].cpu(), per_step, opt
+
+
+@pytest.mark.parametrize("geom", ["a", "b"])
+def test_epocher_matches_the_reference_run(golden, monkeypatch, geom):
+    """fp32, 3 iterations against the reference's UDATrainEpocher with the output MI term (tests/golden/midl.npz): (a) padding 1 and
+    one whole-map window, (b) padding 3 and 9 overlapping 32-pixel patches.  Step-1 gradients at the first-iteration bounds of
+    test_gpu_step, per-step losses, the decoder tail after the last step, the meters."""
+    g = golden("midl")
+    res, grad, per_step, opt = _golden_run(g, geom, monkeypatch)
+    names = [str(n) for n in g["param_names"]]
+    named = dict(zip(names, opt.flat.given))
+    assert len(named) == len(opt.flat.given)
+    worst = {}
+    for n in names:
+        p = named[n]
+        o = opt.flat.offset_of(p)
+        got = grad[o:o + p.numel()].numpy().reshape(-1).astype(np.float64)
+        fp = synth.fp_unpack(g, f"{geom}/grad_step1/{n}")
+        got = got[synth.sample_index(got.size, f"{geom}/grad_step1/{n}")]
+        ref = fp["sample"].astype(np.float64)
+        worst[n] = float(np.linalg.norm(got - ref) / (np.linalg.norm(ref) + 1e-30))
+    _dump(f"golden_grad_{geom}", worst)
+    # the first-iteration bounds of test_gpu_step; measured on the logits layer: (a) 1.8e-5, (b) 6.1e-6.  (a)'s single 64 x 64 window
+    # makes the MI gradient a small difference of entropies, computed in fp32 on both sides
+    assert max(v for k, v in worst.items() if k.startswith("DeConv")) < 2e-5, worst
+    tail = sorted(v for k, v in worst.items() if k.startswith(("Up_conv2", "DeConv")))
+    assert tail[len(tail) // 2] < 5e-3 and tail[-1] < 1.5e-2, tail
+    assert max(worst.values()) < 3e-2, worst
+    assert len(per_step) == 3
+    p = f"{geom}/"
+    np.testing.assert_allclose(per_step[0]["sup_loss"], g[p + "sup_loss"][0], rtol=2e-5)
+    np.testing.assert_allclose(per_step[0]["uda"], g[p + "uda"][0], rtol=2e-4)
+    np.testing.assert_allclose(per_step[0]["mi"], -g[p + "mi_loss"][0], rtol=2e-4)
+    ref_reg = float(g["cfg/cons_weight"]) * g[p + "uda"][0] + float(g["cfg/iic_weight"]) * g[p + "mi_loss"][0]
+    np.testing.assert_allclose(per_step[0]["reg_loss"], ref_reg, rtol=2e-4, atol=1e-7)
+    np.testing.assert_allclose([s["sup_loss"] for s in per_step], g[p + "sup_loss"], rtol=3e-3)
+    np.testing.assert_allclose([s["uda"] for s in per_step], g[p + "uda"], rtol=2e-2)
+    np.testing.assert_allclose([-s["mi"] for s in per_step], g[p + "mi_loss"], rtol=2e-2)
+    # the decoder tail after 3 Adam steps: near-zero gradients' signs move a weight by up to 2 lr per step
+    for n, q in named.items():
+        if not n.startswith(("Up_conv2", "DeConv_1x1")):
+            continue
+        fp = synth.fp_unpack(g, f"{geom}/param_after/{n}")
+        got = q.detach().cpu().numpy().reshape(-1).astype(np.float64)[synth.sample_index(q.numel(), f"{geom}/param_after/{n}")]
+        assert np.abs(got - fp["sample"]).max() <= 7.5e-3, (n, np.abs(got - fp["sample"]).max())
+    keys = [str(k) for k in g[p + "meter_keys"]]
+    got = {f"{k}/{kk}": float(vv) for k, v in res.items() for kk, vv in dict(v).items()}
+    assert sorted(got) == sorted(keys), (sorted(got), sorted(keys))
+    ref = dict(zip(keys, (float(v) for v in g[p + "meter_values"])))
+    np.testing.assert_allclose(got["sup_loss/mean"], ref["sup_loss/mean"], rtol=3e-3)
+    np.testing.assert_allclose(got["uda/mean"], ref["uda/mean"], rtol=2e-2)
+    np.testing.assert_allclose(got["mi/mean"], ref["mi/mean"], rtol=2e-2)
+    np.testing.assert_allclose(got["reg_loss/mean"], ref["reg_loss/mean"], rtol=2e-2)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3. the tape
+def build(dtype="float32", num_batches=7, padding=1, patch_size=1024, iic_weight=1.0):
+    from deepclustering2.loss import KL_div
+    from deepclustering2.optim import Adam
+    from semi_seg.epocher import MIDLTrainEpocher
+    from semi_seg.synthetic import SyntheticPairs
+    model = _unet(dtype, 41)
+    opt = Adam(model.parameters(), lr=1e-3, weight_decay=1e-5)
+    lab = SyntheticPairs(2, 64, 4, seed=0, device=DEV)
+    unl = SyntheticPairs(2, 64, 4, seed=1, device=DEV)
+    ep = MIDLTrainEpocher(model, opt, iter(lab), iter(unl), KL_div(verbose=False), torch.nn.MSELoss(), num_batches, 0, DEV,
+                          feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25], cons_weight=5.0, iic_weight=iic_weight,
+                          padding=padding, patch_size=patch_size)
+    return ep, model, opt
+
+
+def _run_steps(dtype, tape, steps=7, **kw):
+    import bench
+    from miseg_amd import ops
+    ops.set_mi_precision("fp32" if dtype == "float32" else "f16f8")
+    ep, model, opt = build(dtype, **kw)
+    ep._TAPE_DEFAULT = False
+    drv = bench.StepDriver(ep)
+    if tape:
+        ep.enable_step_tape(warmup=2)
+    random.seed(11)
+    for _ in range(steps):
+        drv.step()
+    drv.close()
+    tp = ep._step_tape
+    info = None if tp is None else (tp.replays, tp.disabled, bool(tp.handle), tp.op_names())
+    st = {"param": opt.flat.flat_param.detach().clone(), "m": opt._m[0].detach().clone(), "v": opt._v[0].detach().clone(),
+          "meters": repr(dict(ep.meters.tracking_status()))}
+    ep.disable_step_tape()
+    ops.set_mi_precision("fp32")
+    return st, info
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
+def test_midl_tape_replay_equals_eager_steps(dtype):
+    """2 eager + 1 recorded + 4 replayed iterations give the parameters, Adam's moments and the meters of 7 eager ones, bit for bit.
+    The recorded iteration has no ATen launch (the tape would have been refused) and one launch of each new entry point; the MI term
+    adds into the consistency gradient (no assemble / add of its own)."""
+    got, info = _run_steps(dtype, True)
+    ref, _ = _run_steps(dtype, False)
+    assert info is not None and info[1] is None, f"the tape was refused: {info[:3]}"
+    assert info[2] and info[0] == 4, f"expected 2 eager + 1 recorded + 4 replayed iterations: {info[:3]}"
+    names = info[3]
+    assert names.count("miseg_iic_out_joint_fwd") == 1 and names.count("miseg_iic_out_bwd") == 1, names
+    assert names.count("miseg_softmax_mse") == 1, names
+    for k in ("param", "m", "v"):
+        assert torch.equal(got[k], ref[k]), (k, float((got[k] - ref[k]).abs().max()))
+    assert got["meters"] == ref["meters"], (got["meters"], ref["meters"])
+
+
+def test_changed_mi_settings_rerecord_the_tape():
+    ep, _, _ = build()
+    sig = ep._tape_signature()
+    ep._iic_weight = 0.5
+    assert ep._tape_signature() != sig
+    sig = ep._tape_signature()
+    ep._mi_criterion.padding = 2
+    assert ep._tape_signature() != sig
+    sig = ep._tape_signature()
+    ep._mi_criterion._patch_size, ep._mi_criterion._step_size = (32, 32), (16, 16)
+    assert ep._tape_signature() != sig
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4. out of envelope
+@pytest.mark.parametrize("c,pad", [(12, 1), (4, 5)])
+def test_fallback_outside_the_envelope_matches_float64(c, pad):
+    """C = 12 or padding 5: the epocher composes torch softmax and the generic criterion; loss and gradients match float64."""
+    from contrastyou.losses.iic_loss import IIDSegmentationSmallPathLoss
+    from miseg_amd import ops
+    from semi_seg.epocher import MIDLTrainEpocher
+    ops.set_mi_precision("fp32")
+    ep = MIDLTrainEpocher.__new__(MIDLTrainEpocher)
+    ep._mi_criterion = IIDSegmentationSmallPathLoss(padding=pad, patch_size=24)
+    a, b, masks = _inputs(c, 2, 40, 40, seed=c + pad)
+    ref_mi, ref_ga, ref_gb = _reference(a, b, masks, pad, 24)
+    ad, bd = a.to(DEV).requires_grad_(), b.to(DEV).requires_grad_()
+    loss = ep._mi(ad, bd, torch.tensor(masks, dtype=torch.int32, device=DEV))
+    assert isinstance(loss, torch.Tensor)            # the composed path (the fused one returns a symbolic LinearLoss)
+    loss.backward()
+    assert abs(float(loss) - ref_mi) < 1e-5 * abs(ref_mi)
+    assert _rel(ad.grad.cpu().double(), ref_ga) < 1e-4 and _rel(bd.grad.cpu().double(), ref_gb) < 1e-4
+
+
+def test_taped_epocher_outside_the_envelope_stays_eager_with_a_warning():
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        st, info = _run_steps("float32", True, steps=6, padding=5)
+    assert info is not None and info[1] is not None and not info[2] and info[0] == 0, info[:3]
+    assert any("launch tape not used" in str(w.message) for w in caught), [str(w.message) for w in caught]
+    assert torch.isfinite(st["param"]).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5. the CLI
+def _cli(save, extra, epochs=2):
+    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    shutil.rmtree(run_dir, ignore_errors=True)
+    res = subprocess.run(
+        [sys.executable, "semi_seg/main.py", "Trainer.name=midl", f"Trainer.save_dir={save}", "Trainer.device=cuda",
+         f"Trainer.max_epoch={epochs}", "Trainer.num_batches=3", "Data.size=64", "LabeledData.batch_size=2", "UnlabeledData.batch_size=2"]
+        + extra, cwd=PKG, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    return run_dir
+
+
+@pytest.mark.parametrize("dtype,extra", [("bfloat16", []), ("float16", []),
+                                         ("bfloat16", ["MIDLPaperParameters.padding=3", "MIDLPaperParameters.patch_size=32"])])
+def test_main_cli_runs_midl(golden, dtype, extra):
+    """``python semi_seg/main.py Trainer.name=midl``: two tiny epochs; config.yaml, last.pth and a storage CSV with uda and mi columns;
+    the checkpoint's key tree is the uda trainer's (tests/golden/trainer_io.npz) plus the mi history; inference() runs on it."""
+    save = f"pytest_cli_midl_{dtype}_{len(extra)}_{os.getpid()}"
+    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    try:
+        _cli(save, [f"Arch.compute_dtype={dtype}"] + extra)
+        files = set(os.listdir(run_dir))
+        assert {"config.yaml", "last.pth", "storage.csv"} <= files, files
+        header = open(os.path.join(run_dir, "storage.csv")).read().splitlines()[0].split(",")
+        assert any(h.startswith("tra_uda") for h in header) and any(h.startswith("tra_mi") for h in header), header
+        ck = torch.load(os.path.join(run_dir, "last.pth"), map_location="cpu", weights_only=False)
+        # the uda tree plus the mi history (and, in fp16 mode, the loss scaler every trainer's optimiser carries there)
+        mine = sorted(l for l in synth.tree_lines(ck) if not l.startswith(("_storage/tra_mi", "_optimizer/loss_scaler/")))
+        assert any(l.startswith("_storage/tra_mi") for l in synth.tree_lines(ck))
+        ref = sorted(str(x) for x in golden("trainer_io")["uda/tree_last_pth"])
+        assert mine == ref, (sorted(set(mine) - set(ref))[:12], sorted(set(ref) - set(mine))[:12])
+        if extra:
+            import yaml
+            cfg = yaml.safe_load(open(os.path.join(run_dir, "config.yaml")))
+            assert cfg["MIDLPaperParameters"]["padding"] == 3 and cfg["MIDLPaperParameters"]["patch_size"] == 32
+        if dtype == "bfloat16" and not extra:
+            code = ("import os, sys; from semi_seg.main import build_trainer; tr = build_trainer(sys.argv[1:]); "
+                    "res, score = tr.inference(os.environ['MIDL_CKPT']); assert 0.0 <= score <= 1.0, score; print('inference', score)")
+            res = subprocess.run([sys.executable, "-c", code, "Trainer.name=midl", f"Trainer.save_dir={save}_inf", "Trainer.device=cuda",
+                                  "Trainer.max_epoch=2", "Trainer.num_batches=3", "Data.size=64", "LabeledData.batch_size=2",
+                                  "UnlabeledData.batch_size=2", f"Arch.compute_dtype={dtype}"],
+                                 cwd=PKG, capture_output=True, text=True, timeout=600,
+                                 env={**os.environ, "MIDL_CKPT": os.path.join(run_dir, "last.pth")})
+            assert res.returncode == 0 and "inference" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
+    finally:
+        shutil.rmtree(run_dir, ignore_errors=True)
+        shutil.rmtree(run_dir + "_inf", ignore_errors=True)
