@@ -2180,6 +2180,7 @@ static int conv3x3_wgrad_impl(void* stream, int dt, const void* in0, int64_t C0,
         // narrow layers (measured per shape, scratch/time_conv.py): the lean 16x16-tile kernel wins when one side has <= 16
         // channels (256^2 16->16: 125 -> 52 us, 32->16: 129 -> 83, 128^2 16->32: 85 -> 48) and for 32->64 (71 -> 53);
         // from 32->32 up the 32x32-tile kernel's operand reuse wins
+        // (tests/exact_ref.py wgrad_kernel() mirrors this choice to name its cases by kernel: change both together)
         const bool narrow = Cout % 16 == 0 && (std::min(Cin, Cout) <= 16 || (Cin == 32 && Cout == 64));
         if (narrow || Cout <= 16) {
             const size_t lbc = (size_t)(WG_TH * WG_TW + (WG_TH + 2) * (WG_TW + 2)) * 16 * 2 + (bl.gy ? kBwdCoefRows * 16 * 4 : 0);
