@@ -316,9 +316,16 @@ int miseg_head_global_var_bwd(void* stream, int dt, int64_t B, int64_t H, int64_
  * softmax_klcons: the `UDARegCriterion.name: kl` form of the same term (ref semi_seg/trainer.py:137,194 with
  *              whl:deepclustering2/loss/kl_losses.py:107-126): mean_{n,h,w} sum_c -t*log((p+1e-16)/(t+1e-16)),
  *              p = softmax(a), t = softmax(flip(b)) detached.  Same arguments as softmax_mse.
+ * softmax_entropy: the `EntropyMinParameters` regulariser (Trainer.name=entmin), whl:deepclustering2/loss/kl_losses.py:20-49
+ *              `Entropy(reduction="mean", eps=1e-16)` on softmax(logits): loss = mean_{n,h,w} -sum_c p*log(p+1e-16);
+ *              glogits (may be NULL: forward only) = upstream * d/dlogits, d/dz_c = p_c*(g_c - sum_k g_k p_k)/npix with
+ *              g_c = -(log(p_c+1e-16) + p_c/(p_c+1e-16)).  Class counts 2-6, 8, 10, 16 (as the other pixel losses);
+ *              anything else, or an empty batch, returns MISEG_E_INVALID and launches nothing.
  * `upstream` = fp32 device scalar (may be NULL = 1.0).  Results are deterministic (two-pass sums).
  * ------------------------------------------------------------------------------------------ */
 int64_t miseg_loss_ws_bytes(int64_t N, int64_t H, int64_t W);
+int miseg_softmax_entropy(void* stream, const float* logits, int64_t N, int64_t H, int64_t W, int64_t C,
+                          const float* upstream, float* loss, float* glogits, void* ws, int64_t ws_bytes);
 int miseg_softmax_klcons(void* stream, const float* a, const float* b, const int32_t* flips, int64_t N, int64_t H,
                          int64_t W, int64_t C, const float* upstream, float* loss, float* ga, void* ws, int64_t ws_bytes);
 int miseg_softmax_kl(void* stream, const float* logits, const int64_t* labels, int64_t N, int64_t H, int64_t W,

@@ -126,6 +126,40 @@ __global__ __launch_bounds__(kLT) void softmax_klcons_kernel(const float* __rest
     if (threadIdx.x == 0) partials[blockIdx.x] = part;
 }
 
+// Entropy of the softmax (whl:deepclustering2/loss/kl_losses.py:20-49 on softmax(logits), the `EntropyMinParameters` regulariser):
+// mean_pix -sum_c p_c log(p_c + eps), eps = 1e-16.  d/dp_c = g_c = -(log(p_c + eps) + p_c / (p_c + eps)); through the softmax
+// Jacobian d/dz_c = p_c (g_c - <g, p>).
+template <int C>
+__global__ __launch_bounds__(kLT) void softmax_entropy_kernel(const float* __restrict__ logits, int64_t npix,
+                                                              const float* __restrict__ upstream, float* __restrict__ partials,
+                                                              float* __restrict__ glogits) {
+    __shared__ float red[17];
+    const float up = (upstream ? upstream[0] : 1.f) / (float)npix;
+    const float eps = 1e-16f;
+    float part = 0.f;
+    for (int64_t i = blockIdx.x * (int64_t)kLT + threadIdx.x; i < npix; i += (int64_t)gridDim.x * kLT) {
+        float z[C], p[C], g[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) z[c] = logits[i * C + c];
+        softmax_c(z, C, p);
+        float e = 0.f, dot = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float lg = logf(p[c] + eps);
+            e += -p[c] * lg;
+            g[c] = -(lg + p[c] / (p[c] + eps));
+            dot += g[c] * p[c];
+        }
+        part += e;
+        if (glogits) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) glogits[i * C + c] = up * p[c] * (g[c] - dot);
+        }
+    }
+    part = block_sum(part, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = part;
+}
+
 __global__ __launch_bounds__(256) void finish_sum_kernel(const float* __restrict__ partials, int n, float scale, float* __restrict__ out) {
     __shared__ float red[17];
     // independent loads first (a dependent load-add chain over 8 partials per thread was ~50 us of pure latency), fixed order
@@ -323,6 +357,24 @@ extern "C" int miseg_softmax_klcons(void* stream, const float* a, const float* b
     MISEG_DISPATCH_C(C, L)
 #undef L
     MISEG_LAUNCH_CHECK("softmax_klcons_kernel");
+    hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nb, 1.0f / (float)npix, loss);
+    MISEG_LAUNCH_CHECK("finish_sum_kernel");
+    return MISEG_OK;
+}
+
+extern "C" int miseg_softmax_entropy(void* stream, const float* logits, int64_t N, int64_t H, int64_t W, int64_t C,
+                                     const float* upstream, float* loss, float* glogits, void* ws, int64_t ws_bytes) {
+    MISEG_TAPE(miseg_softmax_entropy, stream, logits, N, H, W, C, upstream, loss, glogits, ws, ws_bytes);
+    MISEG_REQUIRE(logits && loss && ws, "softmax_entropy: null pointer");
+    MISEG_REQUIRE(N >= 0 && H >= 0 && W >= 0, "softmax_entropy: bad shape");
+    const int64_t npix = N * H * W;
+    MISEG_REQUIRE(npix > 0 && ws_bytes >= miseg_loss_ws_bytes(N, H, W), "softmax_entropy: bad shape / workspace");
+    const int nb = loss_blocks(npix);
+    hipStream_t st = as_stream(stream);
+#define L(CC) hipLaunchKernelGGL(softmax_entropy_kernel<CC>, dim3(nb), dim3(kLT), 0, st, logits, npix, upstream, (float*)ws, glogits)
+    MISEG_DISPATCH_C(C, L)
+#undef L
+    MISEG_LAUNCH_CHECK("softmax_entropy_kernel");
     hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nb, 1.0f / (float)npix, loss);
     MISEG_LAUNCH_CHECK("finish_sum_kernel");
     return MISEG_OK;

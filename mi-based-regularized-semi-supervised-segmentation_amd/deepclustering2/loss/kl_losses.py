@@ -2,7 +2,8 @@
 
 ``KL_div()(prob, target)`` keeps the reference call form.  On the train-step hot path the epocher calls
 ``KL_div.from_logits(logits, labels)`` instead, which is the fused HIP kernel (softmax + one-hot + KL +
-mean, and its backward) -- numerically the same expression evaluated in one pass.
+mean, and its backward) -- numerically the same expression evaluated in one pass.  ``Entropy.from_logits(logits)``
+is the same for ``Entropy()(softmax(logits, 1))`` (the ``entmin`` trainer's regulariser).
 """
 from __future__ import annotations
 
@@ -65,3 +66,12 @@ class Entropy(nn.Module):
         assert simplex(input)
         e = -(input * (input + self._eps).log()).sum(1)
         return e.mean() if self._reduction == "mean" else e.sum() if self._reduction == "sum" else e
+
+    def supports_fused(self) -> bool:
+        return self._reduction == "mean" and self._eps == 1e-16
+
+    def from_logits(self, logits: Tensor) -> Tensor:
+        """== self(softmax(logits, 1)) in one fused HIP kernel (+ fused backward)."""
+        from miseg_amd import ops
+        assert self.supports_fused()
+        return ops.softmax_entropy(logits)

@@ -910,6 +910,42 @@ def softmax_kl_consistency(a: Tensor, b: Tensor, flips: Optional[Tensor] = None)
     return _SoftmaxKLCons.apply(a, b, flips)
 
 
+_LOSS_CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)     # MISEG_DISPATCH_C of csrc/losses.hip
+
+
+def softmax_entropy_supported(c: int) -> bool:
+    """Whether ``softmax_entropy`` has a kernel for ``c`` classes (the pixel losses' dispatch list: 2-6, 8, 10, 16)."""
+    return int(c) in _LOSS_CLASS_COUNTS
+
+
+class _SoftmaxEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits: Tensor):
+        _need_gpu(logits)
+        raw_logits = logits
+        logits = _logits_nhwc(logits)
+        n, c, h, w = logits.shape
+        dev = logits.device
+        loss = scalar_out((), dev)
+        glogits = empty_nhwc(n, c, h, w, torch.float32, dev)
+        ws = _ws(query("miseg_loss_ws_bytes", n, h, w), dev)
+        call("miseg_softmax_entropy", _stream(), _ptr(logits), n, h, w, c, None, _ptr(loss), _ptr(glogits), _ptr(ws), ws.numel())
+        ctx.save_for_backward(glogits)
+        ctx.part = _split_part_of(raw_logits, logits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (glogits,) = ctx.saved_tensors
+        return _scaled_grad(ctx.part, glogits, g)
+
+
+def softmax_entropy(logits: Tensor) -> Tensor:
+    """Entropy(reduction='mean', eps=1e-16)(softmax(logits, 1)) = mean_{n,h,w} -sum_c p_c log(p_c + 1e-16), one fused kernel with its
+    backward; a per-sample flip of the logits does not change it.  Class counts: ``softmax_entropy_supported``."""
+    return _SoftmaxEntropy.apply(logits)
+
+
 def output_local_mi_supported(c: int, pad: int) -> bool:
     """Whether ``output_local_mi`` has a fused kernel for ``c`` classes and this padding (2 <= c <= 8, 0 <= pad <= 3)."""
     return int(_cabi.lib().miseg_iic_out_joint_ws_bytes(1, int(c), 1, 1, int(pad), 1)) >= 0
@@ -1077,7 +1113,8 @@ def _scaled_grad(part, grad: Tensor, g: Tensor) -> Tensor:
     if part is not None and g.dim() == 0 and g.dtype == torch.float32 and g.is_cuda and grad.dtype == torch.float32 and grad.numel() % 4 == 0:
         holder, idx = part
         dst = holder.rows(idx)
-        if dst.dtype == grad.dtype and dst.shape == grad.shape and dst.stride() == grad.stride():
+        # (the launch stores 16-byte vectors: rows that start off such a boundary -- odd map sizes -- take the torch product below)
+        if dst.dtype == grad.dtype and dst.shape == grad.shape and dst.stride() == grad.stride() and dst.data_ptr() % 16 == 0:
             call("miseg_assemble_rows", _stream(), _ptr(dst), _ptr(grad), _ptr(g), grad.numel(), None, None, 0, None, None, 0)
             holder.filled.add(idx)
             return dst
@@ -1118,7 +1155,7 @@ class _SplitRows(torch.autograd.Function):
         for n, g in zip(ctx.sizes, grads):
             part = out.narrow(0, o, n)
             if g is None:
-                if part.is_cuda and n:
+                if part.is_cuda and n and part.data_ptr() % 16 == 0:     # (the library's fill wants a 16-byte boundary)
                     fill_zero(part)
                 else:
                     part.zero_()

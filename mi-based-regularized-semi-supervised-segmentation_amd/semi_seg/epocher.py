@@ -32,7 +32,7 @@ from contrastyou.trainer._utils import ClusterHead  # noqa
 from deepclustering2.augment.tensor_augment import TensorRandomFlip
 from deepclustering2.decorator import FixRandomSeed
 from deepclustering2.epoch import _Epocher  # noqa
-from deepclustering2.loss import KL_div
+from deepclustering2.loss import Entropy, KL_div
 from deepclustering2.meters2 import (AverageValueMeter, EpochResultDict, MeterInterface, MultipleAverageValueMeter, SurfaceMeter,
                                      UniversalDice)
 from deepclustering2.optim import get_lrs_from_optimizer
@@ -923,3 +923,44 @@ class MIDLTrainEpocher(UDATrainEpocher):
         super()._record(host, inter, union, label_group)
         if "mi" in host:
             self.meters["mi"].add(host["mi"])
+
+
+class EntropyMinEpocher(TrainEpocher):
+    """``entmin``: the ``partial`` iteration (same flips, same ``[labeled | unlabeled | flip(unlabeled)]`` forward, same supervised
+    KL) whose regulariser is the entropy of the prediction on the unlabeled batch (``EntropyMinParameters``):
+
+        reg   = Entropy(reduction="mean", eps=1e-16)(softmax(flip(unlabeled_logits)))  = mean_{n,h,w} -sum_c p_c log(p_c + 1e-16)
+        total = sup_loss + reg_weight * reg                  (reg_weight = EntropyMinParameters.weight)
+
+    The mean over pixels does not depend on the flip, so the fused kernel (``ops.softmax_entropy``) reads the ``unlabeled`` rows of
+    the logits batch in place and writes its gradient into those rows of the batch gradient; the ``flip(unlabeled)`` rows get none
+    (``split_rows``' backward zero-fills them).  A class count the kernel does not have (e.g. 7) runs the torch composition
+    eagerly: the launch tape then declines with its usual warning.  Meters: the base ones plus ``entropy``, the unweighted value
+    (``reg_loss`` reports the same number, as ``uda``'s does)."""
+
+    def __init__(self, model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_weight: float, num_batches: int,
+                 cur_epoch: int = 0, device="cpu", feature_position=None, feature_importance=None) -> None:
+        super().__init__(model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_weight, num_batches, cur_epoch,
+                         device, feature_position, feature_importance)
+        self._entropy_criterion = Entropy()
+
+    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
+        meters = super()._configure_meters(meters)
+        meters.register_meter("entropy", AverageValueMeter())
+        return meters
+
+    @_fused
+    def regularization(self, unlabeled_tf_logits: Tensor, unlabeled_logits_tf: Tensor = None, seed=None, *args,
+                       unlabeled_logits: Tensor = None, flips: Tensor = None, **kwargs):
+        crit = self._entropy_criterion
+        if crit.supports_fused() and ops.softmax_entropy_supported(unlabeled_logits.shape[1]):
+            loss = LinearLoss.of(crit.from_logits(unlabeled_logits))
+        else:  # no kernel for this class count: the reference expression on materialised operands (eager; the tape declines)
+            loss = crit(ops.flip(unlabeled_logits, flips).float().softmax(1))
+        self._pending.put("entropy", loss)
+        return loss
+
+    def _record(self, host, inter, union, label_group):
+        super()._record(host, inter, union, label_group)
+        if "entropy" in host:
+            self.meters["entropy"].add(host["entropy"])

@@ -1,7 +1,7 @@
 """The semi-supervised trainers behind ``Trainer.name`` (ref ``semi_seg/trainer.py:24-214``).
 
-Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT, and ``midl``, the
-``MIDLPaperParameters`` section's trainer), the keyword-only constructor, ``init()``,
+Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT, and ``midl`` and
+``entmin``, the ``MIDLPaperParameters`` and ``EntropyMinParameters`` sections' trainers), the keyword-only constructor, ``init()``,
 ``start_training()``, ``inference(checkpoint)``, ``set_feature_positions`` and the attribute names the checkpoint tree is
 keyed by (``_model``, ``_optimizer``, ``_scheduler``, ``_projector_wrappers``, ``_IIDSegWrapper``, ``_storage`` ...; the
 tree itself is pinned by ``tests/golden/trainer_io.npz``).  Config sections are the ones of ``config/semi.yaml``.
@@ -281,5 +281,20 @@ class MIDLTrainer(UDATrainer):
                                   padding=self._mi_padding, patch_size=self._mi_patch_size, **self._epoch_args())
 
 
+class EntropyMinTrainer(SemiTrainer):
+    """``entmin``: + ``EntropyMinParameters.weight`` x the mean entropy of the prediction on the unlabeled batch
+    (``Entropy()(softmax(flip(f(x))))``, one fused kernel).  No new modules -- the criterion is built inside the epocher --, so the
+    checkpoint tree is the ``partial`` trainer's, and validation, test and ``inference`` are ``partial``'s.  Semantics: DESIGN.md
+    section 13."""
+
+    def _init(self) -> None:
+        super()._init()
+        self._reg_weight = float(self._config["EntropyMinParameters"]["weight"])
+
+    def _make_epocher(self):
+        return E.EntropyMinEpocher(self._model, self._optimizer, self._labeled_loader, self._unlabeled_loader, self._sup_criterion,
+                                   reg_weight=self._reg_weight, **self._epoch_args())
+
+
 trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer, "meanteacher": MeanTeacherTrainer,
-                "midl": MIDLTrainer}
+                "midl": MIDLTrainer, "entmin": EntropyMinTrainer}
