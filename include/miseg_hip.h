@@ -648,6 +648,32 @@ int miseg_augment_slices(void* stream, const uint8_t* atlas_img, const uint8_t* 
                          int64_t slice_h, int64_t slice_w, const int32_t* jobs_dev, int64_t njobs, int64_t out_h,
                          int64_t out_w, float* img_out, int64_t* gt_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Contrastive encoder pre-training (Trainer.name=contrast; csrc/contrast.hip)
+ * supcon : ref contrastyou/epocher/contrast_epocher.py:90-95 -- F.normalize(e, dim=1), chunk into views, stack, and
+ *          contrastyou/losses/contrast_loss.py:21-100 SupConLoss(contrast_mode='all') -- in one call, with the gradient with respect
+ *          to the RAW embeddings.  e fp32 [N][D] row-major, N = V*B view-major (rows v*B .. v*B+B-1 are view v); labels int32[B]
+ *          (NULL: SimCLR, labels = 0..B-1).  With b(i) = i mod B:
+ *            z_i  = e_i / max(||e_i||, 1e-12)        s_ij = z_i.z_j / T        m_i = max_j s_ij  (diagonal included)
+ *            Z_i  = sum_{j != i} exp(s_ij - m_i) + 1e-16        P_i = { j != i : labels[b(j)] == labels[b(i)] }
+ *            loss = (T/Tb) * (1/N) * sum_i -(1/|P_i|) sum_{j in P_i} (s_ij - m_i - log Z_i)
+ *            G_ij = (T/Tb)/N * (exp(s_ij - m_i)/Z_i - [j in P_i]/|P_i|) for j != i, G_ii = 0
+ *            gz_i = (1/T) sum_j (G_ij + G_ji) z_j        ge_i = upstream * (gz_i - z_i (z_i.gz_i)) / max(||e_i||, 1e-12)
+ *          `ge` may be NULL (forward only: same loss bits); `upstream` = fp32 device scalar (NULL = 1).  fp32 throughout, no
+ *          floating-point atomics, every sum in a fixed order: two calls give the same bits.  Three launches (normalise | rows of
+ *          s -> loss rows, G | gradient + loss sum).  Range: V >= 2, B >= 1, N = V*B <= 1024, D a multiple of 4, 4 <= D <= 1024;
+ *          anything else returns MISEG_E_INVALID and launches nothing (miseg_supcon_ws_bytes returns -1).
+ * avgpool: the projection head's nn.AdaptiveAvgPool2d((1, 1)) (ref contrastyou/trainer/_utils.py:51,59) on the network's NHWC
+ *          feature map in its storage type `dt`.  fwd: feat [N][H][W][C] -> pooled fp32 [N][C], fp32 accumulation in a fixed order.
+ *          bwd: g fp32 [N][C] -> gfeat [N][H][W][C] of `dt`, every pixel = g / (H*W) (an fp32 division, rounded once to `dt`).
+ *          Any H, W >= 1; C a multiple of 4.
+ * ------------------------------------------------------------------------------------------ */
+int64_t miseg_supcon_ws_bytes(int64_t N, int64_t D);
+int miseg_supcon(void* stream, const float* e, int64_t N, int64_t D, int64_t V, const int32_t* labels, float temperature,
+                 float base_temperature, const float* upstream, float* loss, float* ge, void* ws, int64_t ws_bytes);
+int miseg_avgpool_fwd(void* stream, int dt, const void* feat, int64_t N, int64_t H, int64_t W, int64_t C, float* pooled);
+int miseg_avgpool_bwd(void* stream, int dt, const float* g, int64_t N, int64_t H, int64_t W, int64_t C, void* gfeat);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,30 @@ class UNet(nn.Module):
             return logits, tuple(reversed(enc)), tuple(dec)
         return logits
 
+    def encode(self, x: Tensor, util: str = "Conv5") -> Tensor:
+        """The feature map of component ``util`` (``forward(x, return_features=True)``'s entry of that name), running ONLY the blocks
+        it depends on: ``Conv1..util`` for an encoder position, the encoder and the decoder down to ``util`` otherwise.  Blocks
+        behind ``util`` do not run, so in train mode their BatchNorm running statistics do not move (contrastive pre-training)."""
+        assert util in self.component_names, util
+        enc = []
+        h = x
+        for i in range(1, 6):
+            if i > 1:
+                h = getattr(self, f"Maxpool{i - 1}")(h)
+            h = getattr(self, f"Conv{i}")(h)
+            if util == f"Conv{i}":
+                return h
+            enc.append(h)
+        d = enc[4]
+        for lvl in (5, 4, 3, 2):
+            up = getattr(self, f"Up{lvl}")(d)
+            if util == f"Up{lvl}":
+                return up
+            d = getattr(self, f"Up_conv{lvl}")((enc[lvl - 2], up))
+            if util == f"Up_conv{lvl}":
+                return d
+        return self._head(d)
+
     def _head(self, d: Tensor) -> Tensor:
         # route through the holder's __call__ machinery so hooks registered on DeConv_1x1 fire
         holder = self.DeConv_1x1

@@ -1,4 +1,5 @@
-"""Batch unpackers used by the epochers (ref: contrastyou/epocher/_utils.py:25-33)."""
+"""Batch unpackers used by the epochers (ref: contrastyou/epocher/_utils.py:25-33) and the contrastive label generator (ref :52-69)."""
+from typing import List, Sequence
 
 
 def _to(x, device, non_blocking):
@@ -14,6 +15,26 @@ def preprocess_input_with_twice_transformation(data, device, non_blocking=True):
 
 def preprocess_input_with_single_transformation(data, device, non_blocking=True):
     return data[0][0].to(device, non_blocking=non_blocking), data[0][1].to(device, non_blocking=non_blocking), data[1], data[2], data[3]
+
+
+class GlobalLabelGenerator:
+    """Contrastive class ids of a batch (ref contrastyou/epocher/_utils.py:52-69): per sample, the enabled attributes -- patient
+    first, then partition -- joined as ``"_" + patient`` / ``"_" + partition``; the id is the rank of the sample's string among the
+    batch's sorted unique strings.  Returns a list of ints (they fit int32: at most the batch size)."""
+
+    def __init__(self, contrastive_on_patient: bool = False, contrastive_on_partition: bool = True) -> None:
+        self._contrastive_on_patient = contrastive_on_patient
+        self._contrastive_on_partition = contrastive_on_partition
+
+    def __call__(self, partition_list: Sequence[str], patient_list: Sequence[str]) -> List[int]:
+        assert len(partition_list) == len(patient_list), (len(partition_list), len(patient_list))
+        keys = [""] * len(partition_list)
+        if self._contrastive_on_patient:
+            keys = [k + "_" + str(p) for k, p in zip(keys, patient_list)]
+        if self._contrastive_on_partition:
+            keys = [k + "_" + str(p) for k, p in zip(keys, partition_list)]
+        rank = {k: i for i, k in enumerate(sorted(set(keys)))}
+        return [rank[k] for k in keys]
 
 
 # ---- prediction dumps of the InferenceEpocher (ref: contrastyou/epocher/_utils.py:88-118; skimage.io.imsave -> PIL)

@@ -1,4 +1,4 @@
-"""Cluster heads on the MI355X kernels (ref: contrastyou/trainer/_utils.py:96-168).
+"""Cluster heads and the contrastive projection head on the MI355X kernels (ref: contrastyou/trainer/_utils.py:44-65, :96-168).
 
 ``ClusterHead`` (global: avg-pool -> Linear -> softmax/T) and ``LocalClusterHead`` (per pixel:
 1x1 conv -> channel softmax/T), each with ``num_subheads`` independent sub-heads, same constructor
@@ -9,6 +9,9 @@ epocher's sample gather / flip replay / cat (semi_seg/epocher.py:258-273) into t
 ``head_type='linear'`` with ``normalize=False`` (the shipped config, config/semi.yaml:45-55) runs on the tuned
 kernels of csrc/heads.hip / mi_global.hip; ``head_type='mlp'`` and ``normalize=True`` (ref :106-126, :146-161) run on the
 generic fused kernels of csrc/heads_var.hip (same gather / flip fusion, forward recomputed in the backward).
+
+``ProjectionHead`` (contrastive pre-training: avg-pool -> Linear [-> LeakyReLU -> Linear]) pools the channels_last feature map with
+``ops.avgpool_nhwc`` (csrc/contrast.hip); its one or two small ``nn.Linear`` layers stay on torch.
 """
 from __future__ import annotations
 
@@ -42,6 +45,29 @@ class Normalize(nn.Module):
 
     def forward(self, input):
         return torch.nn.functional.normalize(input, p=2, dim=1)
+
+
+class ProjectionHead(nn.Module):
+    """ref _utils.py:44-65, same Sequential layout (state_dict keys ``_header.2.*`` and, for ``mlp``, ``_header.4.*``): global
+    average pool -> Flatten -> Linear(input_dim, interm_dim) -> LeakyReLU(0.01) -> Linear(interm_dim, output_dim), or a single
+    Linear(input_dim, output_dim) for ``head_type='linear'``.  The pool reads the network's NHWC feature map in its storage type
+    and returns fp32 (``ops.avgpool_nhwc``; GPU only, like every kernel); the Linear layers are fp32 torch modules (2 x 32 x 256 x 256
+    FLOPs at the bench shape).  The ``AdaptiveAvgPool2d`` / ``Flatten`` entries of the Sequential only hold the indices."""
+
+    def __init__(self, input_dim, output_dim, interm_dim=256, head_type="mlp") -> None:
+        super().__init__()
+        assert head_type in ("mlp", "linear"), head_type
+        if head_type == "mlp":
+            tail = [nn.Linear(input_dim, interm_dim), nn.LeakyReLU(0.01, inplace=True), nn.Linear(interm_dim, output_dim)]
+        else:
+            tail = [nn.Linear(input_dim, output_dim)]
+        self._header = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), Flatten(), *tail)
+
+    def forward(self, features: Tensor) -> Tensor:
+        x = ops.avgpool_nhwc(features)
+        for layer in list(self._header)[2:]:
+            x = layer(x)
+        return x
 
 
 _GLOBAL_HIDDEN = 128       # ref _utils.py:120: the pooled mlp head's hidden width is fixed

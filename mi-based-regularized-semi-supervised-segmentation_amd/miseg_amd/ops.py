@@ -946,6 +946,83 @@ def softmax_entropy(logits: Tensor) -> Tensor:
     return _SoftmaxEntropy.apply(logits)
 
 
+_SUPCON_MAX_N, _SUPCON_MAX_D = 1024, 1024     # kSupMaxN / kSupMaxD of csrc/contrast.hip
+
+
+def supcon_supported(n: int, d: int, views: int = 2) -> bool:
+    """Whether ``supcon`` has a kernel for ``n`` = views x batch embedding rows of width ``d`` (the range of ``miseg_supcon``: at
+    least two views of a non-empty batch, n <= 1024, d a multiple of 4 in 4..1024).  Pure host arithmetic."""
+    n, d, views = int(n), int(d), int(views)
+    return views >= 2 and n >= views and n % views == 0 and n <= _SUPCON_MAX_N and 4 <= d <= _SUPCON_MAX_D and d % 4 == 0
+
+
+class _SupCon(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, e: Tensor, labels: Optional[Tensor], views: int, temperature: float, base_temperature: float):
+        _need_gpu(e, labels)
+        if e.dim() != 2:
+            raise ValueError(f"supcon: embeddings must be [views * batch, dim], got {tuple(e.shape)}")
+        e = e.contiguous().float()
+        n, d = e.shape
+        if labels is not None:
+            labels = labels.contiguous().view(-1)
+            if labels.dtype != torch.int32:
+                labels = labels.to(torch.int32)
+            if labels.numel() * views != n:
+                raise ValueError("Num of labels does not match num of features")
+        if not supcon_supported(n, d, views):
+            raise _cabi.MisegError(f"miseg_supcon has no kernel for {n} rows of width {d} in {views} views (ops.supcon_supported)")
+        dev = e.device
+        loss = scalar_out((), dev)
+        want_grad = ctx.needs_input_grad[0]
+        ge = torch.empty_like(e) if want_grad else None
+        ws = _ws(query("miseg_supcon_ws_bytes", n, d), dev)
+        call("miseg_supcon", _stream(), _ptr(e), n, d, int(views), _ptr(labels), float(temperature), float(base_temperature), None,
+             _ptr(loss), _ptr(ge), _ptr(ws), ws.numel())
+        if want_grad:
+            ctx.save_for_backward(ge)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (ge,) = ctx.saved_tensors
+        return ge * g, None, None, None, None
+
+
+def supcon(e: Tensor, labels: Optional[Tensor] = None, views: int = 2, temperature: float = 0.07, base_temperature: float = 0.07) -> Tensor:
+    """``SupConLoss(temperature, 'all', base_temperature)(stack(chunk(F.normalize(e, dim=1), views), 1), labels)`` from the RAW
+    embeddings ``e`` [views * batch, dim] (view-major, as the projector returns them for ``cat([img, img_tf])``) in one library call
+    that also leaves the gradient with respect to ``e``; ``labels`` int [batch], None = SimCLR.  Deterministic.  Shapes:
+    ``supcon_supported``."""
+    return _SupCon.apply(e, labels, int(views), float(temperature), float(base_temperature))
+
+
+class _AvgPoolNHWC(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat: Tensor):
+        _need_gpu(feat)
+        feat = as_nhwc(feat)
+        n, c, h, w = feat.shape
+        pooled = torch.empty(n, c, dtype=torch.float32, device=feat.device)
+        call("miseg_avgpool_fwd", _stream(), _DT[feat.dtype], _ptr(feat), n, h, w, c, _ptr(pooled))
+        ctx.meta = (n, c, h, w, feat.dtype)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        n, c, h, w, dtype = ctx.meta
+        g = g.contiguous().float()
+        gfeat = empty_nhwc(n, c, h, w, dtype, g.device)
+        call("miseg_avgpool_bwd", _stream(), _DT[dtype], _ptr(g), n, h, w, c, _ptr(gfeat))
+        return gfeat
+
+
+def avgpool_nhwc(feature: Tensor) -> Tensor:
+    """``Flatten()(nn.AdaptiveAvgPool2d((1, 1))(feature))`` on the network's channels_last feature map in its storage type (fp32,
+    bf16, fp16) -> fp32 [N, C]; the backward broadcasts ``g / (H * W)`` into a feature gradient of the storage type."""
+    return _AvgPoolNHWC.apply(feature)
+
+
 def output_local_mi_supported(c: int, pad: int) -> bool:
     """Whether ``output_local_mi`` has a fused kernel for ``c`` classes and this padding (2 <= c <= 8, 0 <= pad <= 3)."""
     return int(_cabi.lib().miseg_iic_out_joint_ws_bytes(1, int(c), 1, 1, int(pad), 1)) >= 0

@@ -26,7 +26,7 @@ from torch import Tensor, nn
 
 from contrastyou.epocher._utils import preprocess_input_with_single_transformation  # noqa
 from contrastyou.epocher._utils import preprocess_input_with_twice_transformation  # noqa
-from contrastyou.epocher._utils import write_img_target, write_predict
+from contrastyou.epocher._utils import GlobalLabelGenerator, write_img_target, write_predict
 from contrastyou.helper import average_iter, weighted_average_iter
 from contrastyou.trainer._utils import ClusterHead  # noqa
 from deepclustering2.augment.tensor_augment import TensorRandomFlip
@@ -964,3 +964,73 @@ class EntropyMinEpocher(TrainEpocher):
         super()._record(host, inter, union, label_group)
         if "entropy" in host:
             self.meters["entropy"].add(host["entropy"])
+
+
+class PretrainEncoderEpocher(_Epocher):
+    """``contrast``: contrastive pre-training of the encoder (ref contrastyou/epocher/contrast_epocher.py:21-113, DESIGN.md section
+    14).  One iteration: unpack the two augmented views, ONE train-mode forward of ``cat([img, img_tf])`` up to ``extract_position``
+    (BatchNorm sees the concatenated batch), the projection head, the supervised-contrastive loss of the raw embeddings with the
+    labels of ``group_option`` (``SupConLoss.from_embeddings``: normalisation, loss and gradient in one library call), backward, Adam.
+    The loss is read once per iteration -- before backward, so a NaN raises ``RuntimeError`` with the weights unmoved.  Eager: the
+    launch tape does not record this epocher.  Meters: ``contrastive_loss``, ``lr``.
+
+    Against the reference: the network stops at ``extract_position`` (``UNet.encode``; the reference runs the decoder and discards
+    its output), and the optimiser holds the parameters of ``Conv1..extract_position`` and the projector only (the trainer's
+    ``_trainable``)."""
+
+    def __init__(self, model, projection_head: nn.Module, optimizer: T_optim, pretrain_loader: T_loader, contrastive_criterion: T_loss,
+                 num_batches: int, cur_epoch=0, device="cpu", group_option: str = "partition", extract_position: str = "Conv5") -> None:
+        assert isinstance(num_batches, int) and num_batches > 0, num_batches
+        super().__init__(model, num_batches=num_batches, cur_epoch=cur_epoch, device=device)
+        self._projection_head = projection_head
+        self._optimizer = optimizer
+        self._pretrain_loader = pretrain_loader
+        self._contrastive_criterion = contrastive_criterion
+        assert group_option in ("partition", "patient", "both"), group_option
+        self._group_option = group_option
+        self._label_generator = GlobalLabelGenerator(contrastive_on_patient=group_option in ("patient", "both"),
+                                                     contrastive_on_partition=group_option in ("partition", "both"))
+        net = getattr(model, "module", model)
+        assert extract_position in net.component_names, extract_position
+        self._extract_position = extract_position
+
+    def to(self, device=torch.device("cpu")):
+        super().to(device)
+        self._projection_head.to(self._device)
+
+    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
+        meters.register_meter("contrastive_loss", AverageValueMeter())
+        meters.register_meter("lr", AverageValueMeter())
+        return meters
+
+    def _loss(self, data) -> Tensor:
+        """Forward half of an iteration: the contrastive loss of one batch of the loader (a 0-d tensor with its graph)."""
+        (img, _), (img_tf, _), _filename, partition_list, group_list = preprocess_input_with_twice_transformation(data, self._device)
+        net = getattr(self._model, "module", self._model)
+        feature = net.encode(torch.cat([img, img_tf], dim=0), util=self._extract_position)
+        embeddings = self._projection_head(feature)
+        labels = self._label_generator(partition_list=list(partition_list), patient_list=list(group_list))
+        return self._contrastive_criterion.from_embeddings(embeddings, labels)
+
+    def _step(self, data) -> float:
+        """One iteration; returns the loss value (the iteration's one host read, taken before backward)."""
+        loss = self._loss(data)
+        value = loss.item()
+        if value != value:
+            raise RuntimeError(f"contrastive loss is nan (epoch {self._cur_epoch})")
+        self._optimizer.zero_grad()
+        loss.backward()
+        self._optimizer.step()
+        return value
+
+    def _run(self, *args, **kwargs) -> EpochResultDict:
+        self._model.train()
+        self._projection_head.train()
+        assert self._model.training, self._model.training
+        self.meters["lr"].add(get_lrs_from_optimizer(self._optimizer)[0])
+        report_dict = {}
+        for _, data in zip(self._indicator, self._pretrain_loader):
+            self.meters["contrastive_loss"].add(self._step(data))
+            report_dict = self.meters.tracking_status()
+            self._indicator.set_postfix_dict(report_dict)
+        return report_dict

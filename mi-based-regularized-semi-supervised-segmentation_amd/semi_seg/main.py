@@ -34,11 +34,36 @@ def _place_rank(config) -> int:
     return int(os.environ.get("RANK", 0))
 
 
+def _pretrained_file(pretrained) -> Path:
+    """``Pretrained=<dir | .pth>``: a directory stands for its ``last.pth`` (what ``Trainer.name=contrast`` writes)."""
+    path = Path(pretrained)
+    if path.is_dir():
+        path = path / "last.pth"
+    if not (path.is_file() and path.suffix in (".pth", ".pt")):
+        raise FileNotFoundError(path)
+    return path
+
+
+def load_pretrained(model, pretrained) -> Path:
+    """Copy ONLY the ``_model`` subtree of a checkpoint into ``model``, strictly.  Optimiser, scheduler, ``_buffers`` and history stay
+    behind: fine-tuning starts at epoch 0 with its own schedule (``Checkpoint=`` resumes instead)."""
+    import torch
+    path = _pretrained_file(pretrained)
+    state = torch.load(str(path), map_location="cpu", weights_only=False)
+    if "_model" not in state:
+        raise KeyError(f"{path} has no `_model` entry: not a trainer checkpoint")
+    model.load_state_dict(state["_model"], strict=True)
+    return path
+
+
 def build_trainer(argv=None):
     """Everything of ``main`` up to (not including) the training loop: config, rank placement, loaders, model, trainer,
-    optional checkpoint, data-parallel attachment."""
+    optional pre-trained model (``Pretrained=``) or checkpoint to resume (``Checkpoint=``), data-parallel attachment."""
     cmanager = ConfigManger(Path(PROJECT_PATH) / "config/semi.yaml", argv=argv)
     config = cmanager.config
+    checkpoint, pretrained = config.get("Checkpoint", None), config.get("Pretrained", None)
+    if checkpoint is not None and pretrained is not None:
+        raise ValueError("Pretrained= starts a new run from a checkpoint's model, Checkpoint= resumes one: give one of them")
     rank = _place_rank(config)
     set_benchmark(config.get("RandomSeed", 1))     # identical initial weights on every rank; the data seeds below differ per rank
     size = int(config.get("Data", {}).get("size", 256))
@@ -56,12 +81,13 @@ def build_trainer(argv=None):
         val_loader, test_loader = SyntheticEval(2, 4, size, classes, seed=100), SyntheticEval(2, 4, size, classes, seed=101)
     trainer_name = config["Trainer"].pop("name")
     model = UNet(**config["Arch"])
+    if pretrained is not None:
+        load_pretrained(model, pretrained)
     trainer = trainer_zoos[trainer_name](
         model=model, labeled_loader=iter(labeled_loader), unlabeled_loader=iter(unlabeled_loader), val_loader=val_loader,
         test_loader=test_loader, sup_criterion=KL_div(), configuration={**cmanager.config, **{"GITHASH": gethash(__file__)}},
         **config["Trainer"])
     trainer.init()
-    checkpoint = config.get("Checkpoint", None)
     if checkpoint is not None:
         trainer.load_state_dict_from_path(checkpoint, strict=False)
     trainer.attach_data_parallel()      # no-op for a single process; else bucketed RCCL all-reduce of the flat gradient

@@ -1,7 +1,8 @@
 """The semi-supervised trainers behind ``Trainer.name`` (ref ``semi_seg/trainer.py:24-214``).
 
 Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT, and ``midl`` and
-``entmin``, the ``MIDLPaperParameters`` and ``EntropyMinParameters`` sections' trainers), the keyword-only constructor, ``init()``,
+``entmin``, the ``MIDLPaperParameters`` and ``EntropyMinParameters`` sections' trainers, and ``contrast``, the encoder stage of the
+reference's contrastive pre-training), the keyword-only constructor, ``init()``,
 ``start_training()``, ``inference(checkpoint)``, ``set_feature_positions`` and the attribute names the checkpoint tree is
 keyed by (``_model``, ``_optimizer``, ``_scheduler``, ``_projector_wrappers``, ``_IIDSegWrapper``, ``_storage`` ...; the
 tree itself is pinned by ``tests/golden/trainer_io.npz``).  Config sections are the ones of ``config/semi.yaml``.
@@ -296,5 +297,88 @@ class EntropyMinTrainer(SemiTrainer):
                                    reg_weight=self._reg_weight, **self._epoch_args())
 
 
+class ContrastTrainer(SemiTrainer):
+    """``contrast``: contrastive pre-training of the encoder (the encoder stage of ref contrastyou/trainer/contrast_trainer.py:64-114;
+    DESIGN.md section 14).  ``unlabeled_loader`` is the pre-training loader; the labeled, validation and test loaders are accepted and
+    unused.  One epoch = one ``PretrainEncoderEpocher``, then the scheduler, the history / TensorBoard / ``storage.csv`` and
+    ``last.pth``; nothing is evaluated and no ``best.pth`` is written.  Fine-tune from the result with any other trainer and
+    ``Pretrained=<run dir | .pth>`` (semi_seg/main.py).
+
+    Reads ``ContrastParameters`` (defaults: config/contrast.yaml, merged under the given configuration).  Only ``Conv1 ..
+    extract_position`` and the projector are trained -- and only they are handed to the optimiser, so every other parameter stays bit
+    for bit.  Checkpoints carry ``_model``, ``_projector``, ``_optimizer``, ``_scheduler``, ``_contrastive_criterion``, ``_storage``."""
+
+    DEFAULTS = Path(PROJECT_PATH) / "config" / "contrast.yaml"
+
+    def __init__(self, *, configuration=None, **kwargs):
+        import yaml
+        shipped = yaml.safe_load(open(str(self.DEFAULTS)))["ContrastParameters"]
+        configuration = dict(configuration or {})
+        configuration["ContrastParameters"] = {**shipped, **(configuration.get("ContrastParameters") or {})}
+        super().__init__(configuration=configuration, **kwargs)
+
+    def _init(self) -> None:
+        super()._init()
+        from contrastyou.arch import UNet
+        from contrastyou.losses.contrast_loss import SupConLoss
+        from contrastyou.trainer._utils import ProjectionHead
+        section = self._config["ContrastParameters"]
+        self._group_option, self._extract_position = str(section["group_option"]), str(section["extract_position"])
+        assert self._group_option in ("partition", "patient", "both"), self._group_option
+        if self._extract_position not in UNet.dimension_dict:
+            raise ValueError(f"ContrastParameters.extract_position={self._extract_position}: one of {sorted(UNet.dimension_dict)}")
+        if getattr(self._model, "compute_dtype", torch.float32) == torch.float16:
+            raise NotImplementedError("Trainer.name=contrast has no loss scaling: use Arch.compute_dtype float32 or bfloat16")
+        self._projector = ProjectionHead(input_dim=UNet.dimension_dict[self._extract_position], output_dim=int(section["output_dim"]),
+                                         head_type=str(section["ptype"]))
+        self._contrastive_criterion = SupConLoss(temperature=float(section["temperature"]),
+                                                 base_temperature=float(section["base_temperature"]))
+        self._model.disable_grad_all()
+        self._model.enable_grad(from_="Conv1", util=self._extract_position)
+
+    def _trainable(self):
+        """The parameters of ``Conv1 .. extract_position`` and the projector's.  The reference hands Adam every parameter and relies on
+        ``grad is None`` to skip the rest; the flat fused Adam zero-fills such slots and would still decay them."""
+        blocks = self._model._range("Conv1", self._extract_position)
+        return chain(*(getattr(self._model, name).parameters() for name in blocks), self._projector.parameters())
+
+    def attach_data_parallel(self, num_buckets: int = 3):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise RuntimeError("Trainer.name=contrast runs in a single process: a cross-rank contrastive loss needs an all-gather of the "
+                               "embeddings, which is not implemented")
+        return None
+
+    def _make_epocher(self):
+        return E.PretrainEncoderEpocher(self._model, self._projector, self._optimizer, self._unlabeled_loader, self._contrastive_criterion,
+                                        num_batches=self._num_batches, cur_epoch=self._cur_epoch, device=self._device,
+                                        group_option=self._group_option, extract_position=self._extract_position)
+
+    def _run_epoch(self, *args, **kwargs) -> EpochResultDict:
+        return self._make_epocher().run()
+
+    def _start_training(self) -> None:
+        for epoch in range(self._start_epoch, self._max_epoch):
+            self._cur_epoch = epoch
+            trained = self.run_epoch()
+            scheduler = getattr(self, "_scheduler", None)
+            if scheduler is not None:
+                scheduler.step()
+            record = StorageIncomeDict(tra=trained)
+            self._storage.put_from_dict(record, self._cur_epoch)
+            if self.is_writer:
+                self._writer.add_scalar_with_StorageDict(record, self._cur_epoch)
+                self._save_to("last.pth")
+                self._storage.to_csv(self._save_dir)
+
+    def _eval_epoch(self, *args, **kwargs):
+        raise NotImplementedError("Trainer.name=contrast pre-trains the encoder and evaluates nothing: fine-tune with another trainer and "
+                                  "Pretrained=<this run's directory>, and evaluate that")
+
+    def inference(self, checkpoint=None):  # noqa
+        raise NotImplementedError("Trainer.name=contrast has no segmentation to infer: fine-tune with another trainer and "
+                                  "Pretrained=<this run's directory>, and run inference on that")
+
+
 trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer, "meanteacher": MeanTeacherTrainer,
-                "midl": MIDLTrainer, "entmin": EntropyMinTrainer}
+                "midl": MIDLTrainer, "entmin": EntropyMinTrainer, "contrast": ContrastTrainer}
