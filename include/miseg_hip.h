@@ -674,6 +674,42 @@ int miseg_supcon(void* stream, const float* e, int64_t N, int64_t D, int64_t V, 
 int miseg_avgpool_fwd(void* stream, int dt, const void* feat, int64_t N, int64_t H, int64_t W, int64_t C, float* pooled);
 int miseg_avgpool_bwd(void* stream, int dt, const float* g, int64_t N, int64_t H, int64_t W, int64_t C, void* gfeat);
 
+/* ------------------------------------------------------------------------------------------
+ * Contrastive decoder pre-training (Trainer.name=contrastdecoder; csrc/contrast_decoder.hip): the pieces of the reference's
+ * LocalProjectionHead (ref contrastyou/trainer/_utils.py:68-93: Conv2d(C, 64, 3, 1, 1) + bias, LeakyReLU(0.01), Conv2d(64, 32, 3, 1, 1)
+ * + bias, F.adaptive_max_pool2d) that the bias-free miseg_conv3x3_* kernels leave open, and the unfold_position of
+ * contrastyou/epocher/_utils.py:36-49 as index arithmetic.  NHWC activations of `dt` (fp32, bf16, fp16), fp32 parameters and sums, no
+ * floating-point atomics, every sum in a fixed order (two calls give the same bits), 16-byte accesses along C where C allows (C a
+ * multiple of 4; 16-bit types with C % 8 != 0 move 8 bytes).  Anything outside the stated range returns MISEG_E_INVALID before the
+ * first launch.
+ * bias_lrelu_fwd : y = T(v > 0 ? v : v * slope), v = float(raw) + bias[c] (one fp32 add, one fp32 multiply, not contracted).  y may
+ *                  alias raw.  slope = 1 is the bare bias add.
+ * bias_lrelu_bwd : gx = T(y > 0 ? g : g * slope) with g = float(gy) -- torch's in-place leaky_relu backward, which reads the RESULT --
+ *                  and gbias[c] = the sum over n, h, w of that fp32 value before it is rounded.  gx may alias gy; gx == NULL computes
+ *                  gbias alone.  ws from miseg_bias_lrelu_bwd_ws_bytes (16-byte aligned).  C <= 1024.
+ * bias_amaxpool_fwd : F.adaptive_max_pool2d(raw, (OH, OW)) + bias[c].  Window (oh, ow) = rows floor(oh*H/OH) .. ceil((oh+1)*H/OH),
+ *                  columns likewise.  Among equal maxima the first in row-major order is taken; a NaN beats every number (of several
+ *                  NaNs the last one, as torch's scan leaves it).  idx int32 [N][OH][OW][C] = h*W + w of the element taken.  e is fp32
+ *                  in embedding-row layout: with B = N/V, bh = OH/PH, bw = OW/PW, n = v*B + b, blk = ph*PW + pw, the value of
+ *                  (n, c, ph*bh + dh, pw*bw + dw) goes to row v*PH*PW*B + blk*B + b, column c*bh*bw + dh*bw + dw of
+ *                  e [N*PH*PW][C*bh*bw], value = max + bias[c] (one fp32 add): cat over the views of
+ *                  unfold_position(chunk_v, (PH, PW))[0].view(rows, -1).  PH = PW = V = 1 is contiguous NCHW [N][C][OH][OW].
+ *                  bias == NULL adds nothing.  Range: C % 4 == 0, C <= 1024, OH % PH == 0, OW % PW == 0, N % V == 0,
+ *                  H*W < 2^31, N*OH*OW < 2^31, all sizes >= 1.
+ * bias_amaxpool_bwd : graw [N][H][W][C] of `dt`, EVERY element written once: the sum, in window order, of ge over the windows whose
+ *                  idx names the pixel (adjacent windows overlap when H % OH != 0), zero where none does, rounded once.
+ *                  gbias[c] = the sum of the channel's ge entries in (n, oh, ow) order; gbias may be NULL.
+ * ------------------------------------------------------------------------------------------ */
+int miseg_bias_lrelu_fwd(void* stream, int dt, const void* raw, int64_t N, int64_t H, int64_t W, int64_t C, const float* bias,
+                         float slope, void* y);
+int64_t miseg_bias_lrelu_bwd_ws_bytes(int dt, int64_t N, int64_t H, int64_t W, int64_t C);
+int miseg_bias_lrelu_bwd(void* stream, int dt, const void* y, const void* gy, int64_t N, int64_t H, int64_t W, int64_t C, float slope,
+                         void* gx, float* gbias, void* ws, int64_t ws_bytes);
+int miseg_bias_amaxpool_fwd(void* stream, int dt, const void* raw, int64_t N, int64_t H, int64_t W, int64_t C, const float* bias,
+                            int64_t OH, int64_t OW, int64_t PH, int64_t PW, int64_t V, float* e, int32_t* idx);
+int miseg_bias_amaxpool_bwd(void* stream, int dt, const float* ge, const int32_t* idx, int64_t N, int64_t H, int64_t W, int64_t C,
+                            int64_t OH, int64_t OW, int64_t PH, int64_t PW, int64_t V, void* graw, float* gbias);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,5 @@
-"""Batch unpackers used by the epochers (ref: contrastyou/epocher/_utils.py:25-33) and the contrastive label generator (ref :52-69)."""
+"""Batch unpackers used by the epochers (ref: contrastyou/epocher/_utils.py:25-33), the contrastive label generators (ref :52-86) and
+``unfold_position`` (ref :36-49)."""
 from typing import List, Sequence
 
 
@@ -35,6 +36,40 @@ class GlobalLabelGenerator:
             keys = [k + "_" + str(p) for k, p in zip(keys, partition_list)]
         rank = {k: i for i, k in enumerate(sorted(set(keys)))}
         return [rank[k] for k in keys]
+
+
+def unfold_position(features, partition_num=(4, 4)):
+    """ref contrastyou/epocher/_utils.py:36-49: cut [b, c, h, w] into its ``partition_num`` grid of (h // ph) x (w // pw) blocks,
+    concatenated along the batch in row-major block order -> ([ph * pw * b, c, h // ph, w // pw], the (row, column) pixel offset of
+    each row's block).  The pool kernel writes this layout directly
+    (``LocalProjectionHead.embeddings``); the function is the reference's export and the composition's."""
+    import torch
+    b, _c, h, w = features.shape
+    block_h, block_w = h // partition_num[0], w // partition_num[1]
+    blocks, flags = [], []
+    for top in range(0, h - block_h + 1, block_h):
+        for left in range(0, w - block_w + 1, block_w):
+            blocks.append(features[:, :, top:top + block_h, left:left + block_w])
+            flags.extend([(top, left)] * b)
+    return torch.cat(blocks, dim=0), flags
+
+
+class LocalLabelGenerator(GlobalLabelGenerator):
+    """Contrastive class ids of the unfolded blocks (ref contrastyou/epocher/_utils.py:72-86): ``location_list`` holds one entry per
+    unfolded row (``unfold_position``'s second result), the batch's partitions and patients repeat under it; two rows share an id
+    when patient, partition and block position all agree.  The id is the rank of ``"_" + location + "_" + patient + "_" + partition``
+    among the sorted unique strings."""
+
+    def __init__(self) -> None:
+        super().__init__(True, True)
+
+    def __call__(self, partition_list: Sequence[str], patient_list: Sequence[str], location_list: Sequence) -> List[int]:
+        partition_list, patient_list = [str(x) for x in partition_list], [str(x) for x in patient_list]
+        location_list = [str(x) for x in location_list]
+        repeat = len(location_list) // len(patient_list)
+        partition_list, patient_list = partition_list * repeat, patient_list * repeat
+        assert len(location_list) == len(partition_list), (len(location_list), len(partition_list))
+        return super().__call__([a + "_" + b for a, b in zip(patient_list, partition_list)], location_list)
 
 
 # ---- prediction dumps of the InferenceEpocher (ref: contrastyou/epocher/_utils.py:88-118; skimage.io.imsave -> PIL)

@@ -1,4 +1,4 @@
-"""Cluster heads and the contrastive projection head on the MI355X kernels (ref: contrastyou/trainer/_utils.py:44-65, :96-168).
+"""Cluster heads and the contrastive projection heads on the MI355X kernels (ref: contrastyou/trainer/_utils.py:44-93, :96-168).
 
 ``ClusterHead`` (global: avg-pool -> Linear -> softmax/T) and ``LocalClusterHead`` (per pixel:
 1x1 conv -> channel softmax/T), each with ``num_subheads`` independent sub-heads, same constructor
@@ -11,7 +11,8 @@ kernels of csrc/heads.hip / mi_global.hip; ``head_type='mlp'`` and ``normalize=T
 generic fused kernels of csrc/heads_var.hip (same gather / flip fusion, forward recomputed in the backward).
 
 ``ProjectionHead`` (contrastive pre-training: avg-pool -> Linear [-> LeakyReLU -> Linear]) pools the channels_last feature map with
-``ops.avgpool_nhwc`` (csrc/contrast.hip); its one or two small ``nn.Linear`` layers stay on torch.
+``ops.avgpool_nhwc`` (csrc/contrast.hip); its one or two small ``nn.Linear`` layers stay on torch.  ``LocalProjectionHead`` (decoder
+pre-training: 3x3 conv [-> LeakyReLU -> 3x3 conv] -> adaptive max-pool) runs on ``ops.conv3x3_bias`` / ``bias_lrelu`` / ``bias_amaxpool``.
 """
 from __future__ import annotations
 
@@ -68,6 +69,68 @@ class ProjectionHead(nn.Module):
         for layer in list(self._header)[2:]:
             x = layer(x)
         return x
+
+
+class LocalProjectionHead(nn.Module):
+    """ref _utils.py:68-93, same constructor and Sequential layout (state_dict keys ``_projector.0.*`` and, for ``mlp``,
+    ``_projector.2.*``): Conv2d(input_dim, 64, 3, 1, 1) -> LeakyReLU(0.01) -> Conv2d(64, 32, 3, 1, 1) -> adaptive_max_pool2d, or the
+    first convolution and the pool alone for ``head_type='linear'``.  ``forward`` returns the pooled map [N, Cout, OH, OW] (fp32).
+
+    ``embeddings`` returns what the decoder pre-training epocher feeds the contrastive loss,
+    ``cat_v(unfold_position(chunk_v(forward(x)), partition_num)[0].view(rows, -1))``, written by the pool kernel itself.
+
+    On the GPU the convolutions are the MFMA kernels (``ops.conv3x3_bias``), their biases ride in the passes behind them
+    (``ops.bias_lrelu``, ``ops.bias_amaxpool``; csrc/contrast_decoder.hip) and the feature map stays in its storage type.  CPU tensors
+    and shapes a kernel refuses run the torch composition of the same modules."""
+
+    def __init__(self, input_dim, head_type="mlp", output_size=(4, 4)) -> None:
+        super().__init__()
+        assert head_type in ("mlp", "linear"), head_type
+        self._output_size = tuple(int(v) for v in output_size)
+        if head_type == "mlp":
+            self._projector = nn.Sequential(nn.Conv2d(input_dim, 64, 3, 1, 1), nn.LeakyReLU(0.01, inplace=True), nn.Conv2d(64, 32, 3, 1, 1))
+        else:
+            self._projector = nn.Sequential(nn.Conv2d(input_dim, 64, 3, 1, 1))
+
+    def _kernel_takes(self, features: Tensor, views: int, partition_num) -> bool:
+        if not (features.is_cuda and features.dim() == 4 and features.dtype in (torch.float32, torch.bfloat16, torch.float16)):
+            return False
+        n, _, h, w = features.shape
+        convs = [m for m in self._projector if isinstance(m, nn.Conv2d)]
+        return all(ops.conv3x3_bias_supported(m.in_channels, m.out_channels, features.dtype) and ops.bias_lrelu_supported(m.out_channels)
+                   for m in convs) and features.shape[1] == convs[0].in_channels and \
+            ops.bias_amaxpool_supported(n, convs[-1].out_channels, h, w, self._output_size, partition_num, views)
+
+    def _rows(self, features: Tensor, views: int, partition_num) -> Tensor:
+        first = self._projector[0]
+        raw = ops.conv3x3_bias(features, first.weight)
+        if len(self._projector) == 1:
+            return ops.bias_amaxpool(raw, first.bias, self._output_size, partition_num, views)
+        hidden = ops.bias_lrelu(raw, first.bias, self._projector[1].negative_slope, inplace=True)
+        last = self._projector[2]
+        return ops.bias_amaxpool(ops.conv3x3_bias(hidden, last.weight), last.bias, self._output_size, partition_num, views)
+
+    def _composed(self, features: Tensor) -> Tensor:
+        out = self._projector(features.to(self._projector[0].weight.dtype))
+        return torch.nn.functional.adaptive_max_pool2d(out, output_size=self._output_size)
+
+    def forward(self, features: Tensor) -> Tensor:
+        if not self._kernel_takes(features, 1, (1, 1)):
+            return self._composed(features)
+        rows = self._rows(features, 1, (1, 1))
+        return rows.view(features.shape[0], -1, *self._output_size)
+
+    def embeddings(self, features: Tensor, views: int = 2, partition_num=(2, 2)) -> Tensor:
+        partition_num = tuple(int(v) for v in partition_num)
+        if features.shape[0] % views != 0:
+            raise ValueError(f"`features` needs to hold {views} views of a batch, got {features.shape[0]} samples")
+        if self._output_size[0] % partition_num[0] or self._output_size[1] % partition_num[1]:
+            raise ValueError(f"output_size {self._output_size} is not a multiple of partition_num {partition_num}")
+        if self._kernel_takes(features, views, partition_num):
+            return self._rows(features, views, partition_num)
+        from contrastyou.epocher._utils import unfold_position
+        blocks = [unfold_position(chunk, partition_num)[0] for chunk in torch.chunk(self._composed(features), views, dim=0)]
+        return torch.cat([b.reshape(b.shape[0], -1) for b in blocks], dim=0)
 
 
 _GLOBAL_HIDDEN = 128       # ref _utils.py:120: the pooled mlp head's hidden width is fixed

@@ -1023,6 +1023,160 @@ def avgpool_nhwc(feature: Tensor) -> Tensor:
     return _AvgPoolNHWC.apply(feature)
 
 
+# ------------------------------------------------------------------------------------------ LocalProjectionHead (contrastdecoder)
+_CD_MAX_C = 1024          # kCdMaxC of csrc/contrast_decoder.hip
+
+
+def conv3x3_bias_supported(cin: int, cout: int, dtype=torch.float32) -> bool:
+    """Whether ``conv3x3_bias`` has kernels for a Conv2d(cin, cout, 3, 1, 1) on activations of ``dtype``: whole 16-byte channel
+    vectors on both sides (the range of ``miseg_conv3x3_fwd`` / ``miseg_conv3x3_wgrad`` for a single full-resolution source)."""
+    if dtype not in _DT:
+        return False
+    vec = 4 if dtype == torch.float32 else 8
+    return int(cin) > 0 and int(cout) > 0 and int(cin) % vec == 0 and int(cout) % vec == 0
+
+
+def bias_lrelu_supported(c: int) -> bool:
+    """The channel range of ``miseg_bias_lrelu_fwd/bwd``: a multiple of 4, at most 1024."""
+    return 0 < int(c) <= _CD_MAX_C and int(c) % 4 == 0
+
+
+def bias_amaxpool_supported(n: int, c: int, h: int, w: int, output_size=(4, 4), partition_num=(1, 1), views: int = 1) -> bool:
+    """The range of ``miseg_bias_amaxpool_fwd/bwd``.  Pure host arithmetic."""
+    n, c, h, w, views = int(n), int(c), int(h), int(w), int(views)
+    (oh, ow), (ph, pw) = (int(v) for v in output_size), (int(v) for v in partition_num)
+    return (min(n, h, w, oh, ow, ph, pw, views) >= 1 and bias_lrelu_supported(c) and oh % ph == 0 and ow % pw == 0 and n % views == 0
+            and h * w < 2 ** 31 and n * oh * ow < 2 ** 31)
+
+
+class _Conv3x3Bias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor):
+        from .unet_ops import _pack
+        _need_gpu(x, weight)
+        x = as_nhwc(x)
+        n, cin, h, w = x.shape
+        cout = weight.shape[0]
+        if tuple(weight.shape[1:]) != (cin, 3, 3) or not conv3x3_bias_supported(cin, cout, x.dtype):
+            raise _cabi.MisegError(f"conv3x3_bias has no kernel for a weight {tuple(weight.shape)} on {cin} channels of {x.dtype} "
+                                   "(ops.conv3x3_bias_supported)")
+        raw = empty_nhwc(n, cout, h, w, x.dtype, x.device)
+        call("miseg_conv3x3_fwd", _stream(), _DT[x.dtype], _ptr(x), cin, 0, None, 0, 0, n, h, w, _ptr(_pack(weight, x.dtype, 0)), cout,
+             _ptr(raw), None, work=(18.0 * cin * cout * n * h * w, float(x.element_size()) * n * h * w * (cin + cout)),
+             tag=f"conv3x3_fwd[{h}x{w},{cin}->{cout}]")
+        ctx.save_for_backward(x, weight)
+        ctx.weight_ref = weight          # the Parameter object itself: the pack cache is keyed by it
+        return raw
+
+    @staticmethod
+    def backward(ctx, graw: Tensor):
+        from .unet_ops import _pack
+        x, weight = ctx.saved_tensors
+        n, cin, h, w = x.shape
+        cout, dtype, dev = weight.shape[0], x.dtype, x.device
+        graw = as_nhwc(graw.to(dtype))
+        gx = gw = None
+        if ctx.needs_input_grad[1]:
+            gw = torch.empty_like(weight)
+            ws = _ws(query("miseg_conv3x3_wgrad_ws_bytes", n, h, w, cin, cout), dev)
+            call("miseg_conv3x3_wgrad", _stream(), _DT[dtype], _ptr(x), cin, 0, None, 0, 0, n, h, w, _ptr(graw), cout, _ptr(gw), _ptr(ws), ws.numel(),
+                 work=(18.0 * cin * cout * n * h * w, float(x.element_size()) * n * h * w * (cin + cout)), tag=f"conv3x3_wgrad[{h}x{w},{cin}->{cout}]")
+        if ctx.needs_input_grad[0]:
+            gx = empty_nhwc(n, cin, h, w, dtype, dev)
+            call("miseg_conv3x3_fwd", _stream(), _DT[dtype], _ptr(graw), cout, 0, None, 0, 0, n, h, w, _ptr(_pack(ctx.weight_ref, dtype, 1, 0, cin)), cin,
+                 _ptr(gx), None, work=(18.0 * cin * cout * n * h * w, float(x.element_size()) * n * h * w * (cin + cout)),
+                 tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cin}]")
+        return gx, gw
+
+
+def conv3x3_bias(x: Tensor, weight: Tensor) -> Tensor:
+    """The convolution of a biased ``nn.Conv2d(cin, cout, 3, 1, 1)`` on a channels_last activation of fp32 / bf16 / fp16, WITHOUT its
+    bias: the consumer (``bias_lrelu`` or ``bias_amaxpool``) adds it in the pass it makes anyway and owns its gradient.  Forward, data
+    gradient (pack kind 1) and weight gradient are the MFMA kernels of csrc/conv.hip.  Shapes: ``conv3x3_bias_supported``."""
+    return _Conv3x3Bias.apply(x, weight)
+
+
+class _BiasLReLU(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, raw: Tensor, bias: Tensor, slope: float, inplace: bool):
+        _need_gpu(raw, bias)
+        raw = as_nhwc(raw)
+        n, c, h, w = raw.shape
+        if not bias_lrelu_supported(c) or bias.numel() != c:
+            raise _cabi.MisegError(f"miseg_bias_lrelu_fwd has no kernel for {c} channels and a bias of {bias.numel()} (ops.bias_lrelu_supported)")
+        bias = bias.contiguous().float()
+        y = raw if inplace else torch.empty_like(raw)
+        call("miseg_bias_lrelu_fwd", _stream(), _DT[raw.dtype], _ptr(raw), n, h, w, c, _ptr(bias), float(slope), _ptr(y),
+             work=(0.0, 2.0 * raw.element_size() * raw.numel()), tag=f"bias_lrelu_fwd[{h}x{w},{c}]")
+        if inplace:
+            ctx.mark_dirty(raw)
+        ctx.save_for_backward(y)
+        ctx.slope = float(slope)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy: Tensor):
+        (y,) = ctx.saved_tensors
+        n, c, h, w = y.shape
+        gy = as_nhwc(gy.to(y.dtype))
+        gx = torch.empty_like(y) if ctx.needs_input_grad[0] else None
+        gbias = torch.empty(c, dtype=torch.float32, device=y.device)
+        ws = _ws(query("miseg_bias_lrelu_bwd_ws_bytes", _DT[y.dtype], n, h, w, c), y.device)
+        call("miseg_bias_lrelu_bwd", _stream(), _DT[y.dtype], _ptr(y), _ptr(gy), n, h, w, c, ctx.slope, _ptr(gx), _ptr(gbias), _ptr(ws), ws.numel(),
+             work=(0.0, 3.0 * y.element_size() * y.numel()), tag=f"bias_lrelu_bwd[{h}x{w},{c}]")
+        return gx, gbias, None, None
+
+
+def bias_lrelu(raw: Tensor, bias: Tensor, slope: float = 0.01, inplace: bool = False) -> Tensor:
+    """``F.leaky_relu(raw + bias[None, :, None, None], slope)`` on a channels_last activation in its storage type (fp32 add and
+    multiply, one rounding to the storage type); ``inplace`` overwrites ``raw``.  The backward reads the RESULT, as torch's in-place
+    ``leaky_relu`` does, and returns the bias gradient as a fixed-order fp32 sum.  ``slope=1`` is the bare bias add."""
+    return _BiasLReLU.apply(raw, bias, float(slope), bool(inplace))
+
+
+class _BiasAMaxPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, raw: Tensor, bias: Optional[Tensor], oh: int, ow: int, ph: int, pw: int, views: int):
+        _need_gpu(raw, bias)
+        raw = as_nhwc(raw)
+        n, c, h, w = raw.shape
+        if not bias_amaxpool_supported(n, c, h, w, (oh, ow), (ph, pw), views) or (bias is not None and bias.numel() != c):
+            raise _cabi.MisegError(f"miseg_bias_amaxpool_fwd has no kernel for {tuple(raw.shape)} -> ({oh}, {ow}) in ({ph}, {pw}) blocks of "
+                                   f"{views} views (ops.bias_amaxpool_supported)")
+        if bias is not None:
+            bias = bias.contiguous().float()
+        e = torch.empty(n * ph * pw, c * (oh // ph) * (ow // pw), dtype=torch.float32, device=raw.device)
+        idx = torch.empty(n, oh, ow, c, dtype=torch.int32, device=raw.device)
+        call("miseg_bias_amaxpool_fwd", _stream(), _DT[raw.dtype], _ptr(raw), n, h, w, c, _ptr(bias), oh, ow, ph, pw, views, _ptr(e), _ptr(idx),
+             work=(0.0, float(raw.element_size()) * raw.numel()), tag=f"bias_amaxpool_fwd[{h}x{w},{c}]")
+        ctx.save_for_backward(idx)
+        ctx.meta = (n, c, h, w, oh, ow, ph, pw, views, raw.dtype, bias is not None)
+        ctx.mark_non_differentiable(idx)
+        return e, idx
+
+    @staticmethod
+    def backward(ctx, ge: Tensor, _gidx):
+        (idx,) = ctx.saved_tensors
+        n, c, h, w, oh, ow, ph, pw, views, dtype, has_bias = ctx.meta
+        ge = ge.contiguous().float()
+        graw = empty_nhwc(n, c, h, w, dtype, ge.device)
+        gbias = torch.empty(c, dtype=torch.float32, device=ge.device) if has_bias and ctx.needs_input_grad[1] else None
+        call("miseg_bias_amaxpool_bwd", _stream(), _DT[dtype], _ptr(ge), _ptr(idx), n, h, w, c, oh, ow, ph, pw, views, _ptr(graw), _ptr(gbias),
+             work=(0.0, float(graw.element_size()) * graw.numel()), tag=f"bias_amaxpool_bwd[{h}x{w},{c}]")
+        return graw, gbias, None, None, None, None, None
+
+
+def bias_amaxpool(raw: Tensor, bias: Optional[Tensor], output_size=(4, 4), partition_num=(1, 1), views: int = 1, return_indices: bool = False):
+    """``F.adaptive_max_pool2d(raw, output_size) + bias[None, :, None, None]`` on a channels_last activation in its storage type,
+    returned as the fp32 rows ``cat_v(unfold_position(chunk_v, partition_num)[0].view(rows, -1))`` the contrastive loss reads
+    ([N * PH * PW, C * OH/PH * OW/PW]; ``partition_num=(1, 1), views=1`` is ``[N, C * OH * OW]``, the contiguous NCHW result).  Ties
+    take the first maximum in row-major order, a NaN wins.  The backward writes the whole gradient of ``raw`` (overlapping windows
+    add in window order) and the bias gradient.  Shapes: ``bias_amaxpool_supported``."""
+    (oh, ow), (ph, pw) = (int(v) for v in output_size), (int(v) for v in partition_num)
+    e, idx = _BiasAMaxPool.apply(raw, bias, oh, ow, ph, pw, int(views))
+    return (e, idx) if return_indices else e
+
+
 def output_local_mi_supported(c: int, pad: int) -> bool:
     """Whether ``output_local_mi`` has a fused kernel for ``c`` classes and this padding (2 <= c <= 8, 0 <= pad <= 3)."""
     return int(_cabi.lib().miseg_iic_out_joint_ws_bytes(1, int(c), 1, 1, int(pad), 1)) >= 0

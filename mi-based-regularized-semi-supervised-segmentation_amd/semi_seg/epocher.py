@@ -26,7 +26,7 @@ from torch import Tensor, nn
 
 from contrastyou.epocher._utils import preprocess_input_with_single_transformation  # noqa
 from contrastyou.epocher._utils import preprocess_input_with_twice_transformation  # noqa
-from contrastyou.epocher._utils import GlobalLabelGenerator, write_img_target, write_predict
+from contrastyou.epocher._utils import GlobalLabelGenerator, LocalLabelGenerator, write_img_target, write_predict
 from contrastyou.helper import average_iter, weighted_average_iter
 from contrastyou.trainer._utils import ClusterHead  # noqa
 from deepclustering2.augment.tensor_augment import TensorRandomFlip
@@ -1034,3 +1034,48 @@ class PretrainEncoderEpocher(_Epocher):
             report_dict = self.meters.tracking_status()
             self._indicator.set_postfix_dict(report_dict)
         return report_dict
+
+
+class PretrainDecoderEpocher(PretrainEncoderEpocher):
+    """``contrastdecoder``: contrastive pre-training of the decoder (ref contrastyou/epocher/contrast_epocher.py:116-176, DESIGN.md
+    section 15).  One iteration: unpack the two views (same geometric transform, different colour jitter); draw a seed and, under
+    ``FixRandomSeed(seed)``, one H/W flip mask per sample; ONE train-mode forward of ``cat([flip(img), img_ctf])`` up to
+    ``extract_position``; flip the second half of the feature map with the same masks; ``LocalProjectionHead.embeddings`` (two
+    convolutions, the adaptive max-pool and the 2x2 position unfold, the rows written by the pool kernel); the supervised-contrastive
+    loss with the labels of ``LocalLabelGenerator`` (equal patient, partition and block position); backward, Adam.  Both flips are one
+    ``ops.flip`` over all 2B samples with masks of zero for the half that stays.  The loss is read once per iteration, before backward.
+    Eager: the launch tape does not record this epocher.  Meters: ``contrastive_loss``, ``lr``.
+
+    Against the reference: the network stops at ``extract_position`` and the optimiser holds the parameters of ``enable_grad_from ..
+    extract_position`` and the projector only (the trainer's ``_trainable``)."""
+
+    def __init__(self, model, projection_head: nn.Module, optimizer: T_optim, pretrain_decoder_loader: T_loader, contrastive_criterion: T_loss,
+                 num_batches: int, cur_epoch=0, device="cpu", extract_position: str = "Up_conv3", partition_num=(2, 2)) -> None:
+        super().__init__(model, projection_head, optimizer, pretrain_decoder_loader, contrastive_criterion, num_batches, cur_epoch=cur_epoch,
+                         device=device, group_option="both", extract_position=extract_position)
+        self._label_generator = LocalLabelGenerator()
+        self._transformer = TensorRandomFlip(axis=[1, 2], threshold=0.5)
+        self._partition_num = tuple(int(v) for v in partition_num)
+        self.last_flip_masks = None      # the masks of the latest iteration (tests compare them with the reference's draws)
+
+    def _locations(self, batch: int):
+        """``unfold_position``'s second result for one view of ``batch`` samples: the pixel offset of each row's block in the pooled map."""
+        oh, ow = self._projection_head._output_size
+        bh, bw = oh // self._partition_num[0], ow // self._partition_num[1]
+        return [(top, left) for top in range(0, oh - bh + 1, bh) for left in range(0, ow - bw + 1, bw) for _ in range(batch)]
+
+    def _loss(self, data) -> Tensor:
+        (img, _), (img_ctf, _), _filename, partition_list, group_list = preprocess_input_with_twice_transformation(data, self._device)
+        batch = img.shape[0]
+        seed = random.randint(0, int(1e5))
+        with FixRandomSeed(seed):
+            masks = ops.flip_masks(self._transformer.decisions(batch))
+        self.last_flip_masks = list(masks)
+        still = [0] * batch
+        net = getattr(self._model, "module", self._model)
+        images = ops.flip(torch.cat([img, img_ctf], dim=0), torch.tensor(masks + still, dtype=torch.int32, device=img.device))
+        feature = net.encode(images, util=self._extract_position)
+        feature = ops.flip(feature, torch.tensor(still + masks, dtype=torch.int32, device=img.device))
+        embeddings = self._projection_head.embeddings(feature, views=2, partition_num=self._partition_num)
+        labels = self._label_generator(list(partition_list), list(group_list), self._locations(batch))
+        return self._contrastive_criterion.from_embeddings(embeddings, labels)

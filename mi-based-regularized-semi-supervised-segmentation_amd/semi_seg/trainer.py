@@ -1,8 +1,8 @@
 """The semi-supervised trainers behind ``Trainer.name`` (ref ``semi_seg/trainer.py:24-214``).
 
 Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT, and ``midl`` and
-``entmin``, the ``MIDLPaperParameters`` and ``EntropyMinParameters`` sections' trainers, and ``contrast``, the encoder stage of the
-reference's contrastive pre-training), the keyword-only constructor, ``init()``,
+``entmin``, the ``MIDLPaperParameters`` and ``EntropyMinParameters`` sections' trainers, and ``contrast`` and ``contrastdecoder``, the
+encoder and decoder stages of the reference's contrastive pre-training), the keyword-only constructor, ``init()``,
 ``start_training()``, ``inference(checkpoint)``, ``set_feature_positions`` and the attribute names the checkpoint tree is
 keyed by (``_model``, ``_optimizer``, ``_scheduler``, ``_projector_wrappers``, ``_IIDSegWrapper``, ``_storage`` ...; the
 tree itself is pinned by ``tests/golden/trainer_io.npz``).  Config sections are the ones of ``config/semi.yaml``.
@@ -309,13 +309,19 @@ class ContrastTrainer(SemiTrainer):
     for bit.  Checkpoints carry ``_model``, ``_projector``, ``_optimizer``, ``_scheduler``, ``_contrastive_criterion``, ``_storage``."""
 
     DEFAULTS = Path(PROJECT_PATH) / "config" / "contrast.yaml"
+    SECTION = "ContrastParameters"
+    NAME, STAGE = "contrast", "encoder"
 
     def __init__(self, *, configuration=None, **kwargs):
         import yaml
-        shipped = yaml.safe_load(open(str(self.DEFAULTS)))["ContrastParameters"]
+        shipped = yaml.safe_load(open(str(self.DEFAULTS)))[self.SECTION]
         configuration = dict(configuration or {})
-        configuration["ContrastParameters"] = {**shipped, **(configuration.get("ContrastParameters") or {})}
+        configuration[self.SECTION] = {**shipped, **(configuration.get(self.SECTION) or {})}
         super().__init__(configuration=configuration, **kwargs)
+
+    def _refuse_float16(self) -> None:
+        if getattr(self._model, "compute_dtype", torch.float32) == torch.float16:
+            raise NotImplementedError(f"Trainer.name={self.NAME} has no loss scaling: use Arch.compute_dtype float32 or bfloat16")
 
     def _init(self) -> None:
         super()._init()
@@ -327,8 +333,7 @@ class ContrastTrainer(SemiTrainer):
         assert self._group_option in ("partition", "patient", "both"), self._group_option
         if self._extract_position not in UNet.dimension_dict:
             raise ValueError(f"ContrastParameters.extract_position={self._extract_position}: one of {sorted(UNet.dimension_dict)}")
-        if getattr(self._model, "compute_dtype", torch.float32) == torch.float16:
-            raise NotImplementedError("Trainer.name=contrast has no loss scaling: use Arch.compute_dtype float32 or bfloat16")
+        self._refuse_float16()
         self._projector = ProjectionHead(input_dim=UNet.dimension_dict[self._extract_position], output_dim=int(section["output_dim"]),
                                          head_type=str(section["ptype"]))
         self._contrastive_criterion = SupConLoss(temperature=float(section["temperature"]),
@@ -345,7 +350,7 @@ class ContrastTrainer(SemiTrainer):
     def attach_data_parallel(self, num_buckets: int = 3):
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise RuntimeError("Trainer.name=contrast runs in a single process: a cross-rank contrastive loss needs an all-gather of the "
+            raise RuntimeError(f"Trainer.name={self.NAME} runs in a single process: a cross-rank contrastive loss needs an all-gather of the "
                                "embeddings, which is not implemented")
         return None
 
@@ -372,13 +377,74 @@ class ContrastTrainer(SemiTrainer):
                 self._storage.to_csv(self._save_dir)
 
     def _eval_epoch(self, *args, **kwargs):
-        raise NotImplementedError("Trainer.name=contrast pre-trains the encoder and evaluates nothing: fine-tune with another trainer and "
+        raise NotImplementedError(f"Trainer.name={self.NAME} pre-trains the {self.STAGE} and evaluates nothing: fine-tune with another trainer and "
                                   "Pretrained=<this run's directory>, and evaluate that")
 
     def inference(self, checkpoint=None):  # noqa
-        raise NotImplementedError("Trainer.name=contrast has no segmentation to infer: fine-tune with another trainer and "
+        raise NotImplementedError(f"Trainer.name={self.NAME} has no segmentation to infer: fine-tune with another trainer and "
                                   "Pretrained=<this run's directory>, and run inference on that")
 
 
+class ContrastDecoderTrainer(ContrastTrainer):
+    """``contrastdecoder``: contrastive pre-training of the decoder (the decoder stage of ref
+    contrastyou/trainer/contrast_trainer.py:116-170), between ``contrast`` (``Pretrained=<its run>`` on the way
+    in) and the fine-tune (``Pretrained=<this run>`` on the way out).  One epoch = one ``PretrainDecoderEpocher``; the loop, ``last.pth``
+    and what is refused are ``ContrastTrainer``'s.
+
+    Reads ``ContrastDecoderParameters`` (defaults: config/contrast_decoder.yaml, merged under the given configuration).  Gradients
+    are enabled for ``enable_grad_from .. extract_position`` only, and only those blocks and the projector are handed to the
+    optimiser; the encoder runs in train mode with frozen weights (its BatchNorm running statistics move, as in the reference).  The
+    pre-training loader's recipe is replaced by its ``total_freedom=False`` copy: both views share the geometric transform."""
+
+    DEFAULTS = Path(PROJECT_PATH) / "config" / "contrast_decoder.yaml"
+    SECTION = "ContrastDecoderParameters"
+    NAME, STAGE = "contrastdecoder", "decoder"
+
+    def _init(self) -> None:
+        SemiTrainer._init(self)
+        from contrastyou.arch import UNet
+        from contrastyou.losses.contrast_loss import SupConLoss
+        from contrastyou.trainer._utils import LocalProjectionHead
+        section = self._config[self.SECTION]
+        self._extract_position, self._enable_grad_from = str(section["extract_position"]), str(section["enable_grad_from"])
+        if self._extract_position not in UNet.dimension_dict:
+            raise ValueError(f"{self.SECTION}.extract_position={self._extract_position}: one of {sorted(UNet.dimension_dict)}")
+        names = list(self._model.component_names)
+        if self._enable_grad_from not in names or names.index(self._enable_grad_from) > names.index(self._extract_position):
+            raise ValueError(f"{self.SECTION}.enable_grad_from={self._enable_grad_from}: a block at or before {self._extract_position} in {names}")
+        self._refuse_float16()
+        self._output_size = tuple(int(v) for v in section["output_size"])
+        self._partition_num = tuple(int(v) for v in section["partition_num"])
+        if len(self._output_size) != 2 or len(self._partition_num) != 2 or any(o % p for o, p in zip(self._output_size, self._partition_num)):
+            raise ValueError(f"{self.SECTION}: output_size {self._output_size} must be a multiple of partition_num {self._partition_num}")
+        self._projector = LocalProjectionHead(input_dim=UNet.dimension_dict[self._extract_position], head_type=str(section["ptype"]),
+                                              output_size=self._output_size)
+        self._contrastive_criterion = SupConLoss(temperature=float(section["temperature"]),
+                                                 base_temperature=float(section["base_temperature"]))
+        self._model.disable_grad_all()
+        self._model.enable_grad(from_=self._enable_grad_from, util=self._extract_position)
+        self._use_shared_geometry()
+
+    def _use_shared_geometry(self) -> None:
+        """Give the pre-training loader's dataset the ``total_freedom=False`` copy of its recipe (ref contrast_trainer.py:136-138).
+        Loaders without a recipe (the synthetic ones) yield what they yield."""
+        import dataclasses
+        dataset = getattr(self._unlabeled_loader, "dataset", None)
+        recipe = getattr(dataset, "transform", None)
+        if dataclasses.is_dataclass(recipe) and hasattr(recipe, "total_freedom") and hasattr(dataset, "set_transform"):
+            dataset.set_transform(dataclasses.replace(recipe, total_freedom=False))
+
+    def _trainable(self):
+        """The parameters of ``enable_grad_from .. extract_position`` and the projector's (see ``ContrastTrainer._trainable``)."""
+        blocks = self._model._range(self._enable_grad_from, self._extract_position)
+        return chain(*(getattr(self._model, name).parameters() for name in blocks), self._projector.parameters())
+
+    def _make_epocher(self):
+        return E.PretrainDecoderEpocher(self._model, self._projector, self._optimizer, self._unlabeled_loader, self._contrastive_criterion,
+                                        num_batches=self._num_batches, cur_epoch=self._cur_epoch, device=self._device,
+                                        extract_position=self._extract_position, partition_num=self._partition_num)
+
+
 trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer, "meanteacher": MeanTeacherTrainer,
-                "midl": MIDLTrainer, "entmin": EntropyMinTrainer, "contrast": ContrastTrainer}
+                "midl": MIDLTrainer, "entmin": EntropyMinTrainer, "contrast": ContrastTrainer,
+                "contrastdecoder": ContrastDecoderTrainer}
