@@ -355,6 +355,25 @@ int miseg_cat_flipped(void* stream, const void* a, int64_t Na, const void* b, in
  * ref semi_seg/epocher.py:183 + whl:.../general_dice_meter.py:141-172. pred (int64 [N,H,W]) optional. */
 int miseg_argmax_dice(void* stream, const float* logits, const int64_t* labels, int64_t N, int64_t H, int64_t W,
                       int64_t C, int64_t* pred, int64_t* inter, int64_t* uni);
+/* Surface-distance statistics of class-coded masks pred, target (int64 [N,H,W], unit pixel spacing): what Hausdorff, HD95 and the
+ * average surface distance are made of; ref whl:deepclustering2/meters2/individual_meters/surface_distance.py:9-29 (MedPy 0.4.0
+ * __surface_distances, connectivity 1).  For sample b and class classes[k] (device int32[n_classes], any subset in any order) the
+ * masks are pred[b] == c and target[b] == c; a border pixel is a mask pixel with a 4-neighbour outside the mask (outside the image
+ * counts as outside).  Direction 0 runs over the border pixels of pred and takes the squared Euclidean distance (an exact integer)
+ * to the nearest border pixel of target; direction 1 is the converse.  Per (b, k, direction):
+ *   stats[..][4] = n (border pixels of the source), max_sq, qlo_sq, qhi_sq (the squared distances of rank floor(v) and ceil(v) in
+ *                  ascending order, v = (n - 1) * q in double: numpy's virtual index of np.percentile(.., 100 q)),
+ *   sum_dist[..] = sum of sqrt(sq) over the n pixels, in double, by a fixed tree.
+ * If either mask of a (b, k) is empty, all of its outputs are 0.  Integer atomics only: two calls return the same bits.
+ * Work is bounded by O(H W (H + W)) per pair (a row pass, then a minimum along columns), whatever the masks hold.
+ * H, W <= 512, N * n_classes <= 32767, 0 <= q <= 1; anything else, a null pointer or a short workspace returns MISEG_E_INVALID
+ * and launches nothing (the size query returns -1 for a bad shape). */
+int64_t miseg_surface_stats_ws_bytes(int64_t N, int64_t H, int64_t W, int64_t n_classes);
+int miseg_surface_stats(void* stream, const int64_t* pred, const int64_t* target, int64_t N, int64_t H, int64_t W,
+                        const int32_t* classes, int64_t n_classes, double q,
+                        int64_t* stats,     /* [N, n_classes, 2, 4] : n, max_sq, qlo_sq, qhi_sq */
+                        double*  sum_dist,  /* [N, n_classes, 2]    : sum of sqrt(sq) over the n border pixels */
+                        void* ws, int64_t ws_bytes);
 
 /* The iteration's scalar report in one launch   ref: the .item() reads of semi_seg/epocher.py:115-121 and the inline
  * `if torch.isnan(loss): raise` / `assert simplex(..)` of iic_loss.py:28-29,132-133,184-186.

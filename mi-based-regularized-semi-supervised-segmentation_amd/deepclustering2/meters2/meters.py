@@ -2,12 +2,14 @@
 (ref whl:deepclustering2/meters2/meter_interface.py:41-137, individual_meters/averagemeter.py:7-77,
 individual_meters/general_dice_meter.py:18-188).
 
+``SurfaceMeter`` (HD / HD95 / ASD) takes GPU tensors through the HIP surface-distance kernel.
 ``UniversalDice.add`` keeps the reference signature (class-coded ``pred``/``target`` tensors + group
 names).  On GPU tensors the per-sample per-class intersection/union counts come from the fused HIP
 argmax/Dice kernel when logits are supplied via ``add_logits``; integer counts are bit-exact either way.
 """
 from __future__ import annotations
 
+import os
 from collections import OrderedDict, defaultdict
 from typing import Dict, List, Union
 
@@ -154,30 +156,97 @@ def hausdorff_distance(data1, data2, voxelspacing=None) -> float:
     return max(hd1.max(), hd2.max())
 
 
+def mod_hausdorff_distance(data1, data2, voxelspacing=None, percentile=95) -> float:
+    """The 95th-percentile Hausdorff distance (ref whl:.../surface_distance.py:17-24)."""
+    hd1 = _surface_distances(data1, data2, voxelspacing, connectivity=1)
+    hd2 = _surface_distances(data2, data1, voxelspacing, connectivity=1)
+    return max(np.percentile(hd1, percentile), np.percentile(hd2, percentile))
+
+
+def average_surface_distance(data1, data2, voxelspacing=None) -> float:
+    """MedPy 0.4.0 ``assd`` (ref whl:.../surface_distance.py:27-29): the mean of the two directed mean surface distances."""
+    asd1 = _surface_distances(data1, data2, voxelspacing, connectivity=1).mean()
+    asd2 = _surface_distances(data2, data1, voxelspacing, connectivity=1).mean()
+    return np.mean((asd1, asd2))
+
+
+_SURFACE_PERCENTILE = 95
+
+
+def _lerp_sqrt(n: int, qlo_sq: int, qhi_sq: int, q: float) -> float:
+    """np.percentile(d, 100 q) of n ascending distances given the squares of its two neighbours in rank: numpy's linear method
+    (virtual index v = (n - 1) q, fraction v - floor(v), and its two-sided lerp), in float64."""
+    v = (n - 1) * q
+    t = v - np.floor(v)
+    a, b = np.sqrt(np.float64(qlo_sq)), np.sqrt(np.float64(qhi_sq))
+    return float(b - (b - a) * (1 - t)) if t >= 0.5 else float(a + (b - a) * t)
+
+
 class SurfaceMeter(_Metric):
-    """Per-slice, per-class Hausdorff distance of class-coded masks (ref whl:.../surface_meter.py:20-145, metername
-    ``hausdorff`` -- the one InferenceEpocher registers).  Host-side scipy work, evaluation only."""
+    """Per-slice, per-class surface distance of class-coded masks (ref whl:.../surface_meter.py:20-145): ``hausdorff`` (HD),
+    ``mod_hausdorff`` (MHD, the 95th percentile) or ``average_surface`` (ASD).  Device tensors with unit spacing go through one
+    ``miseg_amd.ops.surface_stats`` call and one download per batch, and the host finishes in float64; CPU tensors, a
+    ``voxelspacing`` and ``MISEG_SURFACE_HOST=1`` take the scipy restatement of MedPy above."""
+
+    meter_choices = {"mod_hausdorff": mod_hausdorff_distance, "hausdorff": hausdorff_distance, "average_surface": average_surface_distance}
+    abbr = {"mod_hausdorff": "MHD", "hausdorff": "HD", "average_surface": "ASD"}
 
     def __init__(self, C=4, report_axises=None, metername: str = "hausdorff") -> None:
-        assert metername == "hausdorff", metername
+        assert metername in self.meter_choices, metername
         assert report_axises is None or isinstance(report_axises, (list, tuple))
         self._C = C
         self._report_axis = list(report_axises) if report_axises is not None else list(range(C))
         assert max(self._report_axis) <= C
-        self._abbr = "HD"
+        self._surface_name = metername
+        self._abbr = self.abbr[metername]
+        self._surface_function = self.meter_choices[metername]
         self.reset()
 
     def reset(self):
         self._mhd, self._n = [], 0
 
-    def add(self, pred: Tensor, target: Tensor, voxelspacing=None):
+    @staticmethod
+    def on_device(pred: Tensor, target: Tensor, voxelspacing=None) -> bool:
+        """GPU slices [N, H, W] with unit spacing, unless ``MISEG_SURFACE_HOST=1``."""
+        return pred.is_cuda and target.is_cuda and pred.dim() == 3 and voxelspacing is None and os.environ.get("MISEG_SURFACE_HOST") != "1"
+
+    @staticmethod
+    def batch_stats(pred: Tensor, target: Tensor, classes):
+        """Host copies (int64 [N, K, 2, 4], float64 [N, K, 2]) of ``ops.surface_stats`` for one batch: one launch, one download.
+        Meters with the same ``report_axises`` may share them (``add(..., stats=)``)."""
+        from miseg_amd import ops
+        stats, sum_dist = ops.surface_stats(pred.detach(), target.detach(), classes, q=_SURFACE_PERCENTILE / 100)
+        block = getattr(stats, "_miseg_block", None)      # both outputs in one allocation
+        if block is None:
+            return stats.cpu().numpy(), sum_dist.cpu().numpy()
+        host = block.cpu()
+        return host[:stats.numel()].view(stats.shape).numpy(), host[stats.numel():].view(torch.float64).view(sum_dist.shape).numpy()
+
+    def _from_stats(self, stats: np.ndarray, sum_dist: np.ndarray) -> np.ndarray:
+        if (stats[..., 0] == 0).any():          # as MedPy: an empty object on either side
+            raise RuntimeError("A supplied array does not contain any binary object.")
+        if self._surface_name == "hausdorff":
+            return np.sqrt(stats[..., 1].max(-1).astype(np.float64))
+        if self._surface_name == "average_surface":
+            return (sum_dist / stats[..., 0]).sum(-1) / 2
+        out = np.zeros(stats.shape[:2])
+        for b in range(stats.shape[0]):
+            for k in range(stats.shape[1]):
+                out[b, k] = max(_lerp_sqrt(int(n), int(lo), int(hi), _SURFACE_PERCENTILE / 100) for n, _, lo, hi in stats[b, k])
+        return out
+
+    def add(self, pred: Tensor, target: Tensor, voxelspacing=None, stats=None):
+        """``stats``: the ``batch_stats`` of this very batch and these ``report_axises``, to share one launch between meters."""
         assert pred.shape == target.shape, f"incompatible shape of `pred` and `target`, given {pred.shape} and {target.shape}."
-        p = pred.detach().cpu().numpy()
-        t = target.detach().cpu().numpy()
-        out = np.zeros([p.shape[0], len(self._report_axis)])
-        for b in range(p.shape[0]):
-            for k, c in enumerate(self._report_axis):
-                out[b, k] = hausdorff_distance(p[b] == c, t[b] == c, voxelspacing)   # RuntimeError (empty class) aborts the batch
+        if self.on_device(pred, target, voxelspacing):
+            out = self._from_stats(*(stats if stats is not None else self.batch_stats(pred, target, self._report_axis)))
+        else:
+            p = pred.detach().cpu().numpy()
+            t = target.detach().cpu().numpy()
+            out = np.zeros([p.shape[0], len(self._report_axis)])
+            for b in range(p.shape[0]):
+                for k, c in enumerate(self._report_axis):
+                    out[b, k] = self._surface_function(p[b] == c, t[b] == c, voxelspacing)   # RuntimeError (empty class) aborts the batch
         self._mhd.append(out)
         self._n += 1
 

@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("MISEG_LIB_PATH") or os.path.join(PKG_ROOT, "lib", "li
 
 F32, BF16, F16 = 0, 1, 2
 
-_CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "void": None}
+_CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double, "void": None}
 
 
 def _parse_header(path: str = HEADER) -> Dict[str, Tuple[object, List[object]]]:

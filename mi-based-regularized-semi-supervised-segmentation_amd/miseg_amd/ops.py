@@ -1305,6 +1305,32 @@ def argmax_dice(logits: Tensor, labels: Optional[Tensor], want_pred: bool = True
     return pred, inter, uni
 
 
+def surface_stats(pred: Tensor, target: Tensor, classes: Sequence[int], q: float = 0.95, ws: Optional[Tensor] = None):
+    """Surface-distance statistics of class-coded masks ``pred``, ``target`` ([N, H, W] integer device tensors, unit spacing) for the
+    classes listed: ``stats`` int64 [N, len(classes), 2, 4] = (n, max_sq, qlo_sq, qhi_sq) per direction (0: border of pred -> border of
+    target, 1: the converse) and ``sum_dist`` float64 [N, len(classes), 2] (include/miseg_hip.h, miseg_surface_stats).  One library
+    call, no host sync; ``ws``: scratch to use instead of a fresh allocation (the library checks its size)."""
+    _need_gpu(pred, target)
+    if pred.shape != target.shape or pred.dim() != 3:
+        raise ValueError(f"surface_stats: pred and target must both be [N, H, W], got {tuple(pred.shape)} and {tuple(target.shape)}")
+    n, h, w = pred.shape
+    if max(h, w) > 512:      # not a RuntimeError: InferenceEpocher ignores those (an absent class), and this must not pass for one
+        raise ValueError(f"surface_stats: the kernel handles H, W <= 512, got {h} x {w}; MISEG_SURFACE_HOST=1 takes SurfaceMeter's scipy path")
+    dev = pred.device
+    pred, target = pred.contiguous().long(), target.contiguous().long()
+    cls = tuple(int(c) for c in classes)
+    cls_dev = cached_const(("surface_classes", str(dev), cls), lambda: torch.tensor(cls, dtype=torch.int32, device=dev))
+    rows = n * len(cls) * 2
+    block = torch.empty(rows * 5, dtype=torch.int64, device=dev)       # both outputs in one allocation: one copy brings them to the host
+    stats, sum_dist = block[:rows * 4].view(n, len(cls), 2, 4), block[rows * 4:].view(torch.float64).view(n, len(cls), 2)
+    stats._miseg_block = block
+    if ws is None:
+        ws = _ws(query("miseg_surface_stats_ws_bytes", n, h, w, len(cls)), dev)
+    call("miseg_surface_stats", _stream(), _ptr(pred), _ptr(target), n, h, w, _ptr(cls_dev), len(cls), float(q), _ptr(stats),
+         _ptr(sum_dist), _ptr(ws), ws.numel())
+    return stats, sum_dist
+
+
 # ------------------------------------------------------------------------------------------ split with a layout-preserving backward
 _SPLIT_MEMCPY = False   # True: assemble slice gradients with hipMemcpy (slower on a busy device)
 

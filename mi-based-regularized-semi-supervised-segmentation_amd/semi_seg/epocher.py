@@ -219,16 +219,26 @@ class EvalEpocher(_num_class_mixin, _Epocher):
 
 
 class InferenceEpocher(EvalEpocher):
-    """Evaluation that also dumps image / ground truth / prediction PNGs and reports the per-class Hausdorff distance
-    (ref :76-107).  The argmax + Dice counts stay fused on the device; the PNG writes and the Hausdorff distance
-    (scipy) are host work, as in the reference."""
+    """Evaluation that also dumps image / ground truth / prediction PNGs and reports per-class surface distances
+    (ref :76-107): ``surface_metrics`` lists ``SurfaceMeter`` names, registered as ``hd`` (hausdorff, the reference's one),
+    ``mhd`` (mod_hausdorff) and ``asd`` (average_surface).  The argmax + Dice counts stay fused on the device and so do the surface
+    statistics (one ``miseg_surface_stats`` launch per batch, shared by the meters); the PNG writes are host work, as in the reference."""
+
+    SURFACE_METERS = {"hausdorff": "hd", "mod_hausdorff": "mhd", "average_surface": "asd"}
+
+    def __init__(self, model, val_loader: T_loader, sup_criterion: T_loss, cur_epoch=0, device="cpu", surface_metrics=("hausdorff",)) -> None:
+        self._surface_metrics = tuple(surface_metrics)
+        assert all(m in self.SURFACE_METERS for m in self._surface_metrics), surface_metrics
+        super().__init__(model, val_loader, sup_criterion, cur_epoch=cur_epoch, device=device)
 
     def set_save_dir(self, save_dir):
         self._save_dir = save_dir
 
     def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
         meters = super()._configure_meters(meters)
-        meters.register_meter("hd", SurfaceMeter(C=self.num_classes, report_axises=list(range(1, self.num_classes)), metername="hausdorff"))
+        for metername in self._surface_metrics:
+            meters.register_meter(self.SURFACE_METERS[metername],
+                                  SurfaceMeter(C=self.num_classes, report_axises=list(range(1, self.num_classes)), metername=metername))
         return meters
 
     @torch.no_grad()
@@ -248,10 +258,14 @@ class InferenceEpocher(EvalEpocher):
             pred, inter, union = ops.argmax_dice(val_logits, labels, want_pred=True)
             self.meters["loss"].add(val_loss.item())
             self.meters["dice"].add_counts(inter, union, group_name=group)
-            try:                                   # ref: ExceptionIgnorer(RuntimeError) -- a class absent from a slice
-                self.meters["hd"].add(pred, labels)
-            except RuntimeError:
-                pass
+            shared = None                          # the batch's surface statistics: one launch for all the surface meters
+            if len(self._surface_metrics) > 1 and SurfaceMeter.on_device(pred, labels):
+                shared = SurfaceMeter.batch_stats(pred, labels, list(range(1, self.num_classes)))
+            for metername in self._surface_metrics:
+                try:                               # ref: ExceptionIgnorer(RuntimeError) -- a class absent from a slice
+                    self.meters[self.SURFACE_METERS[metername]].add(pred, labels, stats=shared)
+                except RuntimeError:
+                    pass
             report_dict = self.meters.tracking_status()
             self._indicator.set_postfix_dict(report_dict)
         return report_dict, self.meters["dice"].summary()["DSC_mean"]

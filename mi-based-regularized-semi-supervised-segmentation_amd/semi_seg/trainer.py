@@ -162,13 +162,18 @@ class SemiTrainer(Trainer):
     def _inference_model(self) -> nn.Module:
         return self._model
 
-    def inference(self, checkpoint=None):  # noqa
+    def inference(self, checkpoint=None, surface_metrics=None):  # noqa
+        """``surface_metrics``: ``SurfaceMeter`` names to report (``hausdorff`` -> ``hd``, ``mod_hausdorff`` -> ``mhd``,
+        ``average_surface`` -> ``asd``); None reads the optional ``Inference.surface_metrics`` of the configuration, whose default is
+        the reference's ``("hausdorff",)``."""
         if checkpoint is not None and not Path(checkpoint).exists():
             raise AssertionError(checkpoint)         # the reference asserts the path (semi_seg/trainer.py:112-115) before resolving it
         target = _checkpoint_file(checkpoint, self._save_dir)
         self.load_state_dict_from_path(str(target), strict=True)
+        if surface_metrics is None:
+            surface_metrics = (self._config.get("Inference") or {}).get("surface_metrics") or ("hausdorff",)
         runner = E.InferenceEpocher(self._inference_model(), val_loader=self._test_loader, sup_criterion=self._sup_criterion,
-                                    cur_epoch=self._cur_epoch, device=self._device)
+                                    cur_epoch=self._cur_epoch, device=self._device, surface_metrics=tuple(surface_metrics))
         runner.set_save_dir(self._save_dir)
         return runner.run()
 
