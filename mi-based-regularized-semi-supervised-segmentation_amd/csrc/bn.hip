@@ -510,7 +510,6 @@ static inline int ew_blocks(int64_t n) {
     static const int64_t cap = [] { const char* e = getenv("MISEG_EW_BLOCKS"); return e ? atoll(e) : 8192LL; }();      // grid-stride elementwise kernels
     return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), cap));
 }
-static const int64_t kFinishFloats = [] { const char* e = getenv("MISEG_FINISH_FLOATS"); return e ? atoll(e) : 65536LL; }();
 static inline int red_blocks(int64_t npix, int CV) {
     (void)CV;
     static const int cap = [] { const char* e = getenv("MISEG_RED_BLOCKS"); return e ? atoi(e) : 512; }();
@@ -610,7 +609,7 @@ extern "C" int64_t miseg_bn_bwd_ws_bytes(int64_t N, int64_t H, int64_t W, int64_
     return ((int64_t)red_blocks(N * H * W, 1) * 2 * C + 3 * C) * 4;
 }
 
-// reduce (+ finalize) (+ apply): graw == null stops after the statistics, which then leave as bwd_coef for the fused loaders of conv.hip
+// reduce (+ finalize) (+ apply): graw == null stops after the statistics, which then leave as bwd_coef for the fused loaders of the convolutions (conv_tiled.h, conv_stream.hip, conv_wgrad.hip)
 static int bn_relu_bwd_impl(void* stream, int dt, const void* raw, const void* gy, const void* gpool, int64_t N, int64_t H, int64_t W, int64_t C,
                             const float* gamma, const float* saved, int training, void* graw, float* ggamma, float* gbeta, void* ws,
                             int64_t ws_bytes, int32_t* sync_counter, float* bwd_coef, const void* gy2 = nullptr, int64_t n2_begin = 0,

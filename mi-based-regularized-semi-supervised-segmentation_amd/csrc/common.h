@@ -9,7 +9,7 @@
 #include <algorithm>
 
 // ---- the fp16 build -------------------------------------------------------------------------------------------------------
-// bn / conv / heads / heads_var / mi_global are compiled TWICE: as written (16-bit storage type = bf16) and with
+// bn / conv_* / heads / heads_var / mi_global are compiled TWICE: as written (16-bit storage type = bf16) and with
 // -DMISEG_F16_BUILD, where the same sources get IEEE half as their 16-bit type: `bf16` below becomes __half, the conversion helpers
 // and the MFMA builtins switch to their f16 forms, the namespace becomes miseg_f16 and every C entry point is renamed f16_miseg_*
 // (f16_rename.h, generated from the header by the Makefile).  The primary entry points forward dt == MISEG_F16 calls to those
@@ -130,7 +130,7 @@ template <> struct VT<bf16> {
 
 
 // y = T(relu(x)) is > 0 exactly when x exceeds the largest fp32 that T rounds to zero: the ReLU mask of the BatchNorm backward is
-// recomputed from the raw convolution output (bn.hip, conv.hip) and must agree with the activation as it was STORED.
+// recomputed from the raw convolution output (bn.hip, conv_tiled.h, conv_stream.hip) and must agree with the activation as it was STORED.
 template <typename T> __device__ __forceinline__ float relu_keep_threshold();
 template <> __device__ __forceinline__ float relu_keep_threshold<float>() { return 0.f; }
 #ifdef MISEG_F16_BUILD
@@ -139,7 +139,7 @@ template <> __device__ __forceinline__ float relu_keep_threshold<bf16>() { retur
 template <> __device__ __forceinline__ float relu_keep_threshold<bf16>() { return 0x1p-134f; }
 #endif
 
-// BatchNorm backward folded into the convolutions that consume it (conv.hip; coefficients written by bn_bwd_finalize_kernel):
+// BatchNorm backward folded into the convolutions that consume it (conv_tiled.h, conv_stream.hip, conv_wgrad.hip; coefficients written by bn_bwd_finalize_kernel):
 //   graw = m * A * gy + P + Q * (raw - mean),   m = [T(relu(raw * scale + shift)) > 0]
 // with A = gamma * invstd, P = -A * mean(dz), Q = -A * invstd * mean(dz * xhat) (training; P = Q = 0 in eval mode): the tensor
 // bn_bwd_apply_kernel would have written, formed in the loader of the data- / weight-gradient kernel instead.
@@ -257,7 +257,7 @@ __device__ __forceinline__ float* block_column_sums(const float* __restrict__ pa
     return out;
 }
 
-// BatchNorm statistics -> coefficients by the last block of the producing convolution (conv.hip) -- the body of bn_finalize_kernel.
+// BatchNorm statistics -> coefficients by the last block of the producing convolution (conv_tiled.h, conv_stream.hip) -- the body of bn_finalize_kernel.
 struct BnFinish {
     unsigned int* counter;           // null: the caller launches bn_finalize_kernel itself
     const float* gamma; const float* beta; float* rmean; float* rvar; long long* nbt; float* saved;
@@ -316,6 +316,10 @@ __device__ __forceinline__ void bn_finish_block(const float* __restrict__ parts,
         }
     }
 }
+
+// The partial-sum matrix one finishing block reads (bn_finish_block): [parts][2 C] floats.  Above this the separate, C-block bn_finalize
+// is faster.  One constant for the convolutions that produce the statistics (conv_fwd.hip) and the BatchNorm backward (bn.hip).
+inline const int64_t kFinishFloats = [] { const char* e = getenv("MISEG_FINISH_FLOATS"); return e ? atoll(e) : 65536LL; }();
 
 __device__ __forceinline__ float block_min(float v, float* red) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;

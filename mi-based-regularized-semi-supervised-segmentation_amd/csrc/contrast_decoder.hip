@@ -1,5 +1,5 @@
 // Contrastive decoder pre-training (Trainer.name=contrastdecoder): what the reference's LocalProjectionHead needs around the bias-free
-// 3x3 convolution kernels of conv.hip -- bias + LeakyReLU and its backward (with the bias gradient), and the adaptive max-pool with
+// 3x3 convolution kernels of conv_*.hip -- bias + LeakyReLU and its backward (with the bias gradient), and the adaptive max-pool with
 // the bias of the convolution in front of it, written straight into the rows the supervised-contrastive loss reads.
 // ref: contrastyou/trainer/_utils.py:68-93 (LocalProjectionHead), contrastyou/epocher/_utils.py:36-49 (unfold_position),
 // contrastyou/epocher/contrast_epocher.py:149-155 (chunk, unfold, view(b, -1)).

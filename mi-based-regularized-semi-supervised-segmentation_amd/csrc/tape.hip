@@ -344,14 +344,15 @@ extern "C" int miseg_gather_rows(void* stream, const float* src, float* dst, int
     return MISEG_OK;
 }
 
-static inline int ew_blocks(int64_t n16) { return (int)std::max<int64_t>(1, std::min<int64_t>((n16 + 255) / 256, 2048)); }
+// grid of the 16-byte fill / copy / assemble kernels (bn.hip has ew_blocks, another rule: MISEG_EW_BLOCKS)
+static inline int copy_blocks(int64_t n16) { return (int)std::max<int64_t>(1, std::min<int64_t>((n16 + 255) / 256, 2048)); }
 
 extern "C" int miseg_fill_zero(void* stream, void* dst, int64_t nbytes) {
     MISEG_TAPE(miseg_fill_zero, stream, dst, nbytes);
     if (nbytes <= 0) return MISEG_OK;
     MISEG_REQUIRE(dst && (reinterpret_cast<uintptr_t>(dst) & 15) == 0, "fill_zero: destination must be 16-byte aligned");
     const int64_t n16 = nbytes / 16;
-    hipLaunchKernelGGL(miseg::fill_zero_kernel, dim3(ew_blocks(n16)), dim3(256), 0, miseg::as_stream(stream), (uint4*)dst, n16,
+    hipLaunchKernelGGL(miseg::fill_zero_kernel, dim3(copy_blocks(n16)), dim3(256), 0, miseg::as_stream(stream), (uint4*)dst, n16,
                        (unsigned char*)dst + n16 * 16, (int)(nbytes - n16 * 16));
     MISEG_LAUNCH_CHECK("fill_zero_kernel");
     return MISEG_OK;
@@ -362,7 +363,7 @@ extern "C" int miseg_copy(void* stream, void* dst, const void* src, int64_t nbyt
     if (nbytes <= 0) return MISEG_OK;
     MISEG_REQUIRE(dst && src && ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) == 0, "copy: pointers must be 16-byte aligned");
     const int64_t n16 = nbytes / 16;
-    hipLaunchKernelGGL(miseg::copy_kernel, dim3(ew_blocks(n16)), dim3(256), 0, miseg::as_stream(stream), (uint4*)dst, (const uint4*)src, n16,
+    hipLaunchKernelGGL(miseg::copy_kernel, dim3(copy_blocks(n16)), dim3(256), 0, miseg::as_stream(stream), (uint4*)dst, (const uint4*)src, n16,
                        (unsigned char*)dst + n16 * 16, (const unsigned char*)src + n16 * 16, (int)(nbytes - n16 * 16));
     MISEG_LAUNCH_CHECK("copy_kernel");
     return MISEG_OK;
@@ -378,7 +379,7 @@ extern "C" int miseg_assemble_rows(void* stream, float* out, const float* src0, 
     parts.scale[0] = scale0; parts.scale[1] = scale1; parts.scale[2] = scale2;
     parts.end4[0] = numel0 / 4; parts.end4[1] = parts.end4[0] + numel1 / 4; parts.end4[2] = parts.end4[1] + numel2 / 4;
     if (parts.end4[2] == 0) return MISEG_OK;
-    hipLaunchKernelGGL(miseg::assemble_rows_kernel, dim3(ew_blocks(parts.end4[2])), dim3(256), 0, miseg::as_stream(stream), (float4*)out, parts);
+    hipLaunchKernelGGL(miseg::assemble_rows_kernel, dim3(copy_blocks(parts.end4[2])), dim3(256), 0, miseg::as_stream(stream), (float4*)out, parts);
     MISEG_LAUNCH_CHECK("assemble_rows_kernel");
     return MISEG_OK;
 }

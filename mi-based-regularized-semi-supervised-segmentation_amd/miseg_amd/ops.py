@@ -1092,7 +1092,7 @@ class _Conv3x3Bias(torch.autograd.Function):
 def conv3x3_bias(x: Tensor, weight: Tensor) -> Tensor:
     """The convolution of a biased ``nn.Conv2d(cin, cout, 3, 1, 1)`` on a channels_last activation of fp32 / bf16 / fp16, WITHOUT its
     bias: the consumer (``bias_lrelu`` or ``bias_amaxpool``) adds it in the pass it makes anyway and owns its gradient.  Forward, data
-    gradient (pack kind 1) and weight gradient are the MFMA kernels of csrc/conv.hip.  Shapes: ``conv3x3_bias_supported``."""
+    gradient (pack kind 1) and weight gradient are the MFMA kernels of csrc/conv_tiled.hip / conv_stream.hip / conv_wgrad.hip.  Shapes: ``conv3x3_bias_supported``."""
     return _Conv3x3Bias.apply(x, weight)
 
 

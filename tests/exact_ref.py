@@ -175,19 +175,19 @@ HALF = (torch.bfloat16, torch.float16)
 
 
 def conv_streams(dtype, cin, n, h, w) -> bool:
-    """csrc/conv.hip conv_streams(): the persistent streaming kernel serves 16-bit storage, <= 32 input channels, >= 512 16 x 32 tiles."""
+    """csrc/conv.h conv_streams(): the persistent streaming kernel serves 16-bit storage, <= 32 input channels, >= 512 16 x 32 tiles."""
     return dtype in HALF and cin <= 32 and w >= 32 and n * ((h + 15) // 16) * ((w + 31) // 32) >= 512
 
 
 def wgrad_splits(n, h, w, cin, cout):
-    """csrc/conv.hip wgrad_splits(): (8 x 32 tiles, blocks per split, splits)."""
+    """csrc/conv_wgrad.hip wgrad_splits(): (8 x 32 tiles, blocks per split, splits)."""
     ntiles = n * ((h + 7) // 8) * ((w + 31) // 32)
     per = ((cin + 31) // 32) * ((cout + 31) // 32)
     return ntiles, per, min(max(1, 256 // per), ntiles)
 
 
 def wgrad_kernel(dtype, cin, cout) -> str:
-    """csrc/conv.hip conv3x3_wgrad_impl(): which of the three weight-gradient kernels serves the layer."""
+    """csrc/conv_wgrad.hip conv3x3_wgrad_impl(): which of the three weight-gradient kernels serves the layer."""
     if dtype == torch.float32:
         return "fp32"
     narrow = cout % 16 == 0 and (min(cin, cout) <= 16 or (cin == 32 and cout == 64))

@@ -1,4 +1,4 @@
-"""Integer-exact tests of the convolution, weight-gradient, logits-head and BatchNorm kernels (csrc/conv.hip, csrc/bn.hip).
+"""Integer-exact tests of the convolution, weight-gradient, logits-head and BatchNorm kernels (csrc/conv_*.hip, csrc/bn.hip).
 
 The kernels are fed small integers (BatchNorm: dyadic coefficients).  Every operand is exact in bf16, IEEE half and fp32, every
 product and partial sum is an integer below 2^24, so the fp32 accumulators hold them exactly in whatever order a kernel adds, and
@@ -7,7 +7,7 @@ channel, tap, tile or split changes some integer.  Every comparison below is an 
 the range precondition that makes equality the right demand (tests/test_cpu_exact_ref.py proves the same on a machine without a GPU).
 Every call goes through the C ABI (miseg_amd._cabi); outputs are pre-filled with NaN so that an element nobody writes is seen.
 
-Case -> kernel (csrc/conv.hip, csrc/bn.hip; the dispatch predicates are mirrored in exact_ref.py and asserted through the library's
+Case -> kernel (csrc/conv_*.hip, csrc/bn.hip; the dispatch predicates are mirrored in exact_ref.py and asserted through the library's
 own queries).  16-bit = bf16 and, through the -DMISEG_F16_BUILD twins, IEEE half.
   tiled_* / deep_* (H * W < 64^2)            conv3x3_kernel: 16-row tiles, 16 / 32 / 64-channel slices, 16-wide tiles at W < 32; fp32 always
   pt_remainder_64_64 (16-bit, 100 x 200)     conv3x3_pt_kernel: 8-row tiles, 273 tiles over 137 persistent blocks
@@ -519,7 +519,7 @@ def test_bn_relu_backward(name, dtype):
 @pytest.mark.parametrize("name,dtype", pairs(R.DGRAD_BN_CASES))
 def test_batchnorm_backward_folded_into_the_data_gradient(name, dtype):
     """miseg_bn_relu_bwd_stats, then miseg_conv3x3_dgrad_bn with and without gy.  bwd_coef must hold the six rows implied by the exact
-    sums.  The loader (csrc/common.h bn_graw_vec, called from the tile loaders of csrc/conv.hip) forms
+    sums.  The loader (csrc/common.h bn_graw_vec, called from the tile loaders of csrc/conv_tiled.h, conv_stream.hip and conv_wgrad.hip) forms
     graw = [y > 0] * A * gy + P + Q * (raw - mean) in fp32 and PACKS it to the storage type before it reaches the matrix cores: one
     rounding in bf16 / half, none in fp32.  Evaluation mode (P = Q = 0): graw is a multiple of 1/4, nothing is rounded, the data
     gradient is exact.  Training mode: the reference rounds graw once at that same place (exact_ref.dgrad_bn_reference); the cases

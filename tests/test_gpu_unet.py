@@ -54,7 +54,7 @@ def test_conv_bn_relu_layer(dtype, case):
 
 
 # (n, h, w, c0, c1, cout, ups0, pool): every shape has >= 512 16x32 tiles and <= 32 input channels, i.e. goes to
-# conv3x3_stream_kernel<COT, 32, NV, DU> (csrc/conv.hip conv_streams()), forward AND both dgrads; the six instantiations the
+# conv3x3_stream_kernel<COT, 32, NV, DU> (csrc/conv_stream.hip; conv_streams() of csrc/conv.h), forward AND both dgrads; the six instantiations the
 # 256^2 / 128^2 layers of the bench use are all here (16->16, 16->32, 32->32, upsampled 32->16, concat 16+16->16, stem 8->16)
 STREAM_CASES = {
     "s16_16_pool": (4, 256, 256, 16, 0, 16, 0, True),
@@ -75,7 +75,7 @@ def test_conv_bn_relu_layer_streaming_bf16(case, dtype):
     operands, same bounds as the generic kernel above: output within one bf16 ulp, gradients as test_conv_bn_relu_layer."""
     from miseg_amd import _cabi
     n, h, w, c0, c1, cout, ups0, pool = STREAM_CASES[case]
-    assert c0 + c1 <= 32 and n * ((h + 15) // 16) * ((w + 31) // 32) >= 512     # conv_streams() of csrc/conv.hip
+    assert c0 + c1 <= 32 and n * ((h + 15) // 16) * ((w + 31) // 32) >= 512     # conv_streams() of csrc/conv.h
     # the streaming kernel hands BatchNorm one partial per persistent block (<= 512), the generic one a partial per tile
     tiles = n * ((h + 15) // 16) * ((w + 31) // 32)
     assert _cabi.query("miseg_conv3x3_stats_parts", _cabi.BF16 if dtype == torch.bfloat16 else _cabi.F16, c0 + c1, n, h, w) == min(tiles, 512)
@@ -442,7 +442,7 @@ def test_conv3x3_exact_properties_at_full_size(n, h, w, cin, cout, dtype):
             assert float(((pooled.float() - want) / want).abs().max()) <= 2.0 ** -8
 
 
-# ---- BatchNorm backward folded into the convolutions (unet_ops._backward_fused, csrc/conv.hip BNL / RED): a chain of layers, so that
+# ---- BatchNorm backward folded into the convolutions (unet_ops._backward_fused, csrc/conv_tiled_bn.hip, csrc/conv_stream.hip BNL / RED): a chain of layers, so that
 # the second layer's data-gradient kernel forms graw in its loader AND takes the first layer's backward sums in its epilogue.
 # (n, h, w, channel chain, upsample before layer index or None, concat the first activation into layer index or None)
 CHAIN_CASES = {
