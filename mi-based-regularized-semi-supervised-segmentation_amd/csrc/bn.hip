@@ -553,16 +553,22 @@ extern "C" int miseg_bn_relu_fwd(void* stream, int dt, const void* raw, int64_t 
     const int CV = (int)(C / V);
     if (pooled && CV <= 32 && (CV & (CV - 1)) == 0) {     // the coalesced pooled form: the partner lane L ^ CV is in the same wave
         const int nbp = ew_blocks(N * (H / 2) * W * CV);
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
         if (dt == MISEG_F32) hipLaunchKernelGGL(bn_relu_fwd_pool_kernel<float>, dim3(nbp), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)pooled);
-        else if (dt == MISEG_BF16) hipLaunchKernelGGL(bn_relu_fwd_pool_kernel<bf16>, dim3(nbp), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)pooled);
+        else
+#endif
+        if (dt == MISEG_BF16) hipLaunchKernelGGL(bn_relu_fwd_pool_kernel<bf16>, dim3(nbp), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)pooled);
         else return fail(MISEG_E_INVALID, "bn_relu_fwd: bad dtype");
         MISEG_LAUNCH_CHECK("bn_relu_fwd_pool_kernel");
         return MISEG_OK;
     }
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
     if (dt == MISEG_F32) {
         if (pooled) hipLaunchKernelGGL((bn_relu_fwd_kernel<float, true>), dim3(nb), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)pooled);
         else hipLaunchKernelGGL((bn_relu_fwd_kernel<float, false>), dim3(nb), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)nullptr);
-    } else if (dt == MISEG_BF16) {
+    } else
+#endif
+    if (dt == MISEG_BF16) {
         if (pooled) hipLaunchKernelGGL((bn_relu_fwd_kernel<bf16, true>), dim3(nb), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)pooled);
         else hipLaunchKernelGGL((bn_relu_fwd_kernel<bf16, false>), dim3(nb), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)nullptr);
     } else return fail(MISEG_E_INVALID, "bn_relu_fwd: bad dtype");
@@ -588,16 +594,22 @@ extern "C" int miseg_bn_relu_fwd_acc(void* stream, int dt, const void* raw, int6
     const int CV = (int)(C / V);
     if (pooled && CV <= 32 && (CV & (CV - 1)) == 0) {
         const int nbp = ew_blocks(N * (H / 2) * W * CV);
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
         if (dt == MISEG_F32) hipLaunchKernelGGL((bn_relu_fwd_pool_kernel<float, true>), dim3(nbp), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)pooled, a);
-        else if (dt == MISEG_BF16) hipLaunchKernelGGL((bn_relu_fwd_pool_kernel<bf16, true>), dim3(nbp), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)pooled, a);
+        else
+#endif
+        if (dt == MISEG_BF16) hipLaunchKernelGGL((bn_relu_fwd_pool_kernel<bf16, true>), dim3(nbp), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)pooled, a);
         else return fail(MISEG_E_INVALID, "bn_relu_fwd_acc: bad dtype");
         MISEG_LAUNCH_CHECK("bn_relu_fwd_pool_kernel");
         return MISEG_OK;
     }
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
     if (dt == MISEG_F32) {
         if (pooled) hipLaunchKernelGGL((bn_relu_fwd_kernel<float, true, true>), dim3(nb), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)pooled, a);
         else hipLaunchKernelGGL((bn_relu_fwd_kernel<float, false, true>), dim3(nb), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)nullptr, a);
-    } else if (dt == MISEG_BF16) {
+    } else
+#endif
+    if (dt == MISEG_BF16) {
         if (pooled) hipLaunchKernelGGL((bn_relu_fwd_kernel<bf16, true, true>), dim3(nb), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)pooled, a);
         else hipLaunchKernelGGL((bn_relu_fwd_kernel<bf16, false, true>), dim3(nb), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)nullptr, a);
     } else return fail(MISEG_E_INVALID, "bn_relu_fwd_acc: bad dtype");
@@ -637,8 +649,11 @@ static int bn_relu_bwd_impl(void* stream, int dt, const void* raw, const void* g
     MISEG_REQUIRE(!acc || nb <= kBnAccMaxBlocks, "bn_relu_bwd_acc: %d reduce blocks exceed the accumulator's no-wrap bound", nb);
     const int64_t p2lo = n2_begin * H * W, p2hi = n2_end * H * W;
 #define RED(TT, POOL) hipLaunchKernelGGL((bn_relu_bwd_reduce_kernel<TT, POOL>), dim3(nb), dim3(256), lb, st, (const TT*)raw, (const TT*)gy, (const TT*)gpool, (int)N, (int)H, (int)W, (int)C, saved, parts, fin, BnGy2<TT>{(const TT*)gy2, p2lo, p2hi})
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
     if (dt == MISEG_F32) { if (gpool) RED(float, true); else RED(float, false); }
-    else if (dt == MISEG_BF16) { if (gpool) RED(bf16, true); else RED(bf16, false); }
+    else
+#endif
+    if (dt == MISEG_BF16) { if (gpool) RED(bf16, true); else RED(bf16, false); }
     else return fail(MISEG_E_INVALID, "bn_relu_bwd: bad dtype");
 #undef RED
     MISEG_LAUNCH_CHECK("bn_relu_bwd_reduce_kernel");
@@ -652,11 +667,17 @@ static int bn_relu_bwd_impl(void* stream, int dt, const void* raw, const void* g
     const BnBwdAccArgs ba{static_cast<const unsigned long long*>(acc), gamma, ggamma, gbeta, (float)npix, training};
 #define APP(TT, POOL, ACCV) hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, POOL, ACCV>), dim3(na), dim3(256), 0, st, (const TT*)raw, (const TT*)gy, (const TT*)gpool, (int)N, (int)H, (int)W, (int)C, saved, coeffs, (TT*)graw, BnGy2<TT>{(const TT*)gy2, p2lo, p2hi}, ba)
     if (acc) {
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
         if (dt == MISEG_F32) { if (gpool) APP(float, true, true); else APP(float, false, true); }
-        else { if (gpool) APP(bf16, true, true); else APP(bf16, false, true); }
+        else
+#endif
+        { if (gpool) APP(bf16, true, true); else APP(bf16, false, true); }
     } else {
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
         if (dt == MISEG_F32) { if (gpool) APP(float, true, false); else APP(float, false, false); }
-        else { if (gpool) APP(bf16, true, false); else APP(bf16, false, false); }
+        else
+#endif
+        { if (gpool) APP(bf16, true, false); else APP(bf16, false, false); }
     }
 #undef APP
     MISEG_LAUNCH_CHECK("bn_bwd_apply_kernel");
@@ -721,10 +742,12 @@ extern "C" int miseg_bn_relu_bwd_ext(void* stream, int dt, const void* raw, cons
                        coeffs, ggamma, gbeta, (float*)nullptr);
     MISEG_LAUNCH_CHECK("bn_bwd_finalize_kernel");
     const int na = ew_blocks(npix * CV);
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
     if (dt == MISEG_F32)
         hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false>), dim3(na), dim3(256), 0, st, (const float*)raw, (const float*)gy, (const float*)nullptr, (int)N,
                            (int)H, (int)W, (int)C, saved, coeffs, (float*)graw, BnGy2<float>{nullptr, 0, 0});
     else
+#endif
         hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16, false>), dim3(na), dim3(256), 0, st, (const bf16*)raw, (const bf16*)gy, (const bf16*)nullptr, (int)N,
                            (int)H, (int)W, (int)C, saved, coeffs, (bf16*)graw, BnGy2<bf16>{nullptr, 0, 0});
     MISEG_LAUNCH_CHECK("bn_bwd_apply_kernel");
@@ -763,8 +786,11 @@ extern "C" int miseg_sumpool2x2(void* stream, int dt, const void* in, int64_t N,
     MISEG_REQUIRE(C % V == 0, "sumpool2x2: C must be a multiple of %d", V);
     const int64_t total = N * (H / 2) * (W / 2) * (C / V);
     hipStream_t st = as_stream(stream);
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
     if (dt == MISEG_F32) hipLaunchKernelGGL(sumpool2x2_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, st, (const float*)in, (int)N, (int)H, (int)W, (int)C, (float*)out, accumulate);
-    else if (dt == MISEG_BF16) hipLaunchKernelGGL(sumpool2x2_kernel<bf16>, dim3(ew_blocks(total)), dim3(256), 0, st, (const bf16*)in, (int)N, (int)H, (int)W, (int)C, (bf16*)out, accumulate);
+    else
+#endif
+    if (dt == MISEG_BF16) hipLaunchKernelGGL(sumpool2x2_kernel<bf16>, dim3(ew_blocks(total)), dim3(256), 0, st, (const bf16*)in, (int)N, (int)H, (int)W, (int)C, (bf16*)out, accumulate);
     else return fail(MISEG_E_INVALID, "sumpool2x2: bad dtype");
     MISEG_LAUNCH_CHECK("sumpool2x2_kernel");
     return MISEG_OK;
@@ -777,8 +803,11 @@ extern "C" int miseg_axpy(void* stream, int dt, const void* src, void* dst, int6
     const int V = dt == MISEG_BF16 ? 8 : 4;
     MISEG_REQUIRE(numel % V == 0, "axpy: numel must be a multiple of %d", V);
     hipStream_t st = as_stream(stream);
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
     if (dt == MISEG_F32) hipLaunchKernelGGL(axpy_kernel<float>, dim3(ew_blocks(numel / V)), dim3(256), 0, st, (const float*)src, (float*)dst, numel / V);
-    else if (dt == MISEG_BF16) hipLaunchKernelGGL(axpy_kernel<bf16>, dim3(ew_blocks(numel / V)), dim3(256), 0, st, (const bf16*)src, (bf16*)dst, numel / V);
+    else
+#endif
+    if (dt == MISEG_BF16) hipLaunchKernelGGL(axpy_kernel<bf16>, dim3(ew_blocks(numel / V)), dim3(256), 0, st, (const bf16*)src, (bf16*)dst, numel / V);
     else return fail(MISEG_E_INVALID, "axpy: bad dtype");
     MISEG_LAUNCH_CHECK("axpy_kernel");
     return MISEG_OK;
@@ -790,8 +819,11 @@ extern "C" int miseg_cast_pad(void* stream, const float* in, int64_t npix, int64
     MISEG_REQUIRE(in && out && Cin > 0 && CP >= Cin, "cast_pad: bad args");
     hipStream_t st = as_stream(stream);
     const int nb = ew_blocks(npix * CP);
+#ifndef MISEG_F16_BUILD      // dt_out == MISEG_F32 never reaches the fp16 build (conv.h)
     if (dt_out == MISEG_F32) hipLaunchKernelGGL((cast_pad_kernel<float, float>), dim3(nb), dim3(256), 0, st, in, (float*)out, npix, (int)Cin, (int)CP);
-    else if (dt_out == MISEG_BF16 && Cin == 1 && CP == 8) hipLaunchKernelGGL(cast_pad_c1_kernel<bf16>, dim3(ew_blocks(npix)), dim3(256), 0, st, in, (bf16*)out, npix);
+    else
+#endif
+    if (dt_out == MISEG_BF16 && Cin == 1 && CP == 8) hipLaunchKernelGGL(cast_pad_c1_kernel<bf16>, dim3(ew_blocks(npix)), dim3(256), 0, st, in, (bf16*)out, npix);
     else if (dt_out == MISEG_BF16) hipLaunchKernelGGL((cast_pad_kernel<float, bf16>), dim3(nb), dim3(256), 0, st, in, (bf16*)out, npix, (int)Cin, (int)CP);
     else return fail(MISEG_E_INVALID, "cast_pad: bad dtype");
     MISEG_LAUNCH_CHECK("cast_pad_kernel");

@@ -9,7 +9,7 @@
 #include <algorithm>
 
 // ---- the fp16 build -------------------------------------------------------------------------------------------------------
-// bn / conv_* / heads / heads_var / mi_global are compiled TWICE: as written (16-bit storage type = bf16) and with
+// bn / conv_* / heads_* / heads_var / mi_global / contrast* are compiled TWICE: as written (16-bit storage type = bf16) and with
 // -DMISEG_F16_BUILD, where the same sources get IEEE half as their 16-bit type: `bf16` below becomes __half, the conversion helpers
 // and the MFMA builtins switch to their f16 forms, the namespace becomes miseg_f16 and every C entry point is renamed f16_miseg_*
 // (f16_rename.h, generated from the header by the Makefile).  The primary entry points forward dt == MISEG_F16 calls to those

@@ -219,9 +219,11 @@ extern "C" int miseg_avgpool_fwd(void* stream, int dt, const void* feat, int64_t
     AVGPOOL_CHECKS("avgpool_fwd");
     hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)N, (unsigned)cdiv(C, 32));
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
     if (dt == MISEG_F32)
         hipLaunchKernelGGL(avgpool_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)feat, (int)(H * W), (int)C, pooled);
     else
+#endif
         hipLaunchKernelGGL(avgpool_fwd_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)feat, (int)(H * W), (int)C, pooled);
     MISEG_LAUNCH_CHECK("avgpool_fwd_kernel");
     return MISEG_OK;
@@ -237,9 +239,11 @@ extern "C" int miseg_avgpool_bwd(void* stream, int dt, const float* g, int64_t N
     hipStream_t st = as_stream(stream);
     const unsigned chunks = (unsigned)std::min<int64_t>(std::max<int64_t>(cdiv(H * W * (C / 4), 256 * 4), 1), 64);
     const dim3 grid((unsigned)N, chunks);
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
     if (dt == MISEG_F32)
         hipLaunchKernelGGL(avgpool_bwd_kernel<float>, grid, dim3(256), (size_t)C * 4, st, g, (int)(H * W), (int)C, (float*)gfeat);
     else
+#endif
         hipLaunchKernelGGL(avgpool_bwd_kernel<bf16>, grid, dim3(256), (size_t)C * 4, st, g, (int)(H * W), (int)C, (bf16*)gfeat);
     MISEG_LAUNCH_CHECK("avgpool_bwd_kernel");
     return MISEG_OK;

@@ -262,10 +262,15 @@ static inline int cd_vec(int dt, int64_t C) { return dt == MISEG_F32 ? 4 : (C % 
 
 using namespace miseg;
 
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
+#define CD_DISPATCH_F32(dt, LAUNCH) if (dt == MISEG_F32) { LAUNCH(float, 4); } else
+#else
+#define CD_DISPATCH_F32(dt, LAUNCH)
+#endif
 #define CD_DISPATCH(dt, C, LAUNCH)                                  \
     do {                                                            \
-        if (dt == MISEG_F32) { LAUNCH(float, 4); }                  \
-        else if (C % 8 == 0) { LAUNCH(bf16, 8); }                   \
+        CD_DISPATCH_F32(dt, LAUNCH)                                 \
+        if (C % 8 == 0) { LAUNCH(bf16, 8); }                        \
         else { LAUNCH(bf16, 4); }                                   \
     } while (0)
 

@@ -363,9 +363,11 @@ extern "C" int miseg_head_global_fwd(void* stream, int dt, const void* feat, int
     MISEG_REQUIRE(feat && src && w && b && pooled && prob, "head_global_fwd: null pointer");
     MISEG_REQUIRE(K > 0 && K <= 64 && M > 0 && S > 0 && C > 0, "head_global_fwd: bad shape (K<=64)");
     hipStream_t st = as_stream(stream);
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
     if (dt == MISEG_F32)
         hipLaunchKernelGGL(head_pool_kernel<float>, dim3((unsigned)M, (unsigned)cdiv(C, 32)), dim3(256), 0, st, (const float*)feat, (int)(H * W), (int)C, src, pooled);
     else
+#endif
         hipLaunchKernelGGL(head_pool_kernel<bf16>, dim3((unsigned)M, (unsigned)cdiv(C, 32)), dim3(256), 0, st, (const bf16*)feat, (int)(H * W), (int)C, src, pooled);
     MISEG_LAUNCH_CHECK("head_pool_kernel");
     hipLaunchKernelGGL(head_global_fwd_kernel, dim3((unsigned)M, (unsigned)S), dim3(64), 0, st, pooled, (int)M, (int)C, w, b, (int)K, T, prob);
@@ -402,10 +404,12 @@ extern "C" int miseg_head_global_bwd(void* stream, int dt, int64_t B, int64_t H,
     if (gfeat) {
         MISEG_REQUIRE(C % (dt == MISEG_BF16 ? 8 : 4) == 0, "head_global_bwd: C must be a multiple of the 16-byte vector");
         const unsigned fchunks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(16, cdiv(H * W * C / (dt == MISEG_BF16 ? 8 : 4), 256)));
+#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
         if (dt == MISEG_F32)
             hipLaunchKernelGGL(head_global_bwd_feat_kernel<float>, dim3((unsigned)M, fchunks), dim3(256), (size_t)C * 4, st, dz, (int)M,
                                (int)(H * W), (int)C, src, w, (int)S, (int)K, (float*)gfeat);
         else
+#endif
             hipLaunchKernelGGL(head_global_bwd_feat_kernel<bf16>, dim3((unsigned)M, fchunks), dim3(256), (size_t)C * 4, st, dz, (int)M,
                                (int)(H * W), (int)C, src, w, (int)S, (int)K, (bf16*)gfeat);
         MISEG_LAUNCH_CHECK("head_global_bwd_feat_kernel");

@@ -1,7 +1,7 @@
 """float64 references, dyadic input recipes and the dispatch mirror of the cluster-head tests (test_cpu_exact_heads.py,
 test_gpu_exact_heads.py, test_gpu_heads_fp64.py), in the style of exact_ref.py.
 
-The head backward kernels (csrc/heads.hip, csrc/mi_global.hip) take the probabilities and their gradient as INPUTS.  Their arithmetic is
+The head backward kernels (csrc/heads_bwd.hip, csrc/heads_bwd_fused.h, csrc/mi_global.hip) take the probabilities and their gradient as INPUTS.  Their arithmetic is
 dot = sum_k g p, dz = p (g - dot) / T, a hi + lo split of dz and of W into the 16-bit type, matrix-core sums in fp32 and one rounding
 to the storage type.  On dyadic inputs every one of these steps is exact: p = j / den on the simplex, g and the features small integers,
 W small integers (or multiples of 1/64), T a power of two.  Every product and partial sum is then a multiple of one power of two and
@@ -164,7 +164,7 @@ def split(t64, dtype):
 
 # ----------------------------------------------------------------------------------------------------------------- dispatch mirror
 def fwd_instance(dtype, c, s, k, h, w) -> str:
-    """csrc/heads.hip miseg_head_local_fwd(): the kernel instance that serves a shape."""
+    """csrc/heads_fwd.hip miseg_head_local_fwd(): the kernel instance that serves a shape."""
     hw, t = h * w, tname(dtype)
     if dtype in HALF and k == 20 and c in (16, 32) and hw % 4 == 0 and s * k * c <= 3200:
         return f"head_local_fwd_mfma_kernel<{c}>[{t}]"
@@ -190,7 +190,7 @@ def bwd_wave_shape(dtype, c, s, k) -> bool:
 
 
 def bwd_instance(dtype, c, s, k, h, w, m) -> str:
-    """csrc/heads.hip head_local_bwd_impl(): the kernel instance that serves a shape (h, w, m choose no instance, only how often a
+    """csrc/heads_bwd.hip head_local_bwd_impl() and csrc/heads_bwd_fused.h launch_head_bwd_fused_t(): the kernel instance that serves a shape (h, w, m choose no instance, only how often a
     block or a wave loops: bwd_loops)."""
     t = tname(dtype)
     if bwd_wave_shape(dtype, c, s, k):

@@ -1,4 +1,4 @@
-"""Bit-exact tests of the cluster-head backward kernels (csrc/heads.hip, csrc/mi_global.hip) on dyadic data.
+"""Bit-exact tests of the cluster-head backward kernels (csrc/heads_bwd.hip, csrc/heads_bwd_fused.h, csrc/mi_global.hip) on dyadic data.
 
 The backward kernels take prob and gprob as inputs: dot = sum g p, dz = p (g - dot) / T, a hi + lo 16-bit split of dz and W, fp32
 matrix-core sums, one rounding to the storage type.  On the recipes of tests/exact_heads.py (p = j / den on the simplex, integer g and

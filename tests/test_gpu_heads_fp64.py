@@ -1,4 +1,4 @@
-"""Every branch of miseg_head_local_fwd (csrc/heads.hip) against a float64 evaluation of softmax((W f + b) / T) on the gathered, flipped,
+"""Every branch of miseg_head_local_fwd (csrc/heads_fwd.hip) against a float64 evaluation of softmax((W f + b) / T) on the gathered, flipped,
 storage-type-rounded features.  Not exact (the kernels go through exp2 / expf); the bounds are the project's own, those of
 test_gpu_mi.py::test_local_head_forward_mfma_vs_float64: max |d| / (ref + 1e-9) <= 1e-5, max |d| <= 2e-6, no simplex violation, and the
 kernel's fused violation counter equal to the count taken from its output (also with one sub-head poisoned by a NaN bias, where both

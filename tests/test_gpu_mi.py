@@ -488,7 +488,7 @@ def test_head_backward_joins_an_offered_gradient(h, w):
 @pytest.mark.parametrize("c,h,w", [(32, 40, 48), (16, 6, 10), (16, 72, 36)])
 def test_local_head_forward_mfma_vs_float64(c, h, w):
     """The shipped taps (bf16 features, S=5 x K=20, C in {16, 32}) compute the logits on the matrix pipe with the fp32
-    weights split into three bf16 planes (heads.hip: head_local_fwd_mfma_kernel).  Against a float64 evaluation of
+    weights split into three bf16 planes (heads_fwd.hip: head_local_fwd_mfma_kernel).  Against a float64 evaluation of
     softmax((W f + b) / T) on the gathered / flipped features (ref contrastyou/trainer/_utils.py:137-168,
     semi_seg/epocher.py:258-273): 1e-5 relative on the probabilities, the same bound as the fp32 register kernel.
     Shapes: a ragged tail (HW % 1024 != 0), W % 4 != 0, and several blocks per sample."""
