@@ -100,6 +100,31 @@ inline int generic_tile_h(int dt, int64_t H, int64_t W) {
     return H * W >= 64 * 64 ? 8 : 16;
 }
 
+// ---- the tiled kernel's tile shape for a call that does not stream: output channels per block (grid.y slices), tile width, tile
+// height.  THE selection rule: conv3x3_fwd_impl launches by it, the parts queries count blocks by it (the tile does not depend on Cout
+// or pool), and tiled_shape_built below is what it can return.  cot == 0: no such storage type.
+struct TiledShape { int cot, tw, th; };
+inline TiledShape tiled_shape(int dt, int64_t H, int64_t W, int64_t Cout, bool pool) {
+    const int tw = tile_w(W), th = generic_tile_h(dt, H, W);
+    int cot = 0;
+    if (dt == MISEG_BF16 && pool) cot = 64;
+    // 8-row tiles (maps from 64^2 up) take 32 output channels per block: with 64 the weight chunk makes the block's LDS 88 KB -- one
+    // block per CU --, with 32 it is 60 KB and two fit (64^2, same box: 32->64 31.8 -> 26.7 us, 64->64 39.2 -> 36.3, 128->64 55.5 -> 49.9;
+    // the 16-row tiles of the deep layers are one block per CU either way and lose 20 % with the narrower slice)
+    else if (dt == MISEG_BF16) cot = Cout <= 16 ? 16 : (Cout <= 32 || th == 8) ? 32 : 64;
+    else if (dt == MISEG_F32) cot = Cout <= 16 ? 16 : 32;
+    return TiledShape{cot, tw, th};
+}
+// The shapes tiled_shape can return, i.e. the ones the three tiled units are built with (MISEG_TILED_SHAPE, conv_tiled.h):
+//   16-bit: 16 and 32 channels per block on all four tiles, not pooled (a pooled output always takes 64);
+//           64 not pooled on the 16-row tiles only (an 8-row tile takes 32); 64 pooled on all four tiles;
+//   float:  16 and 32 on the 16-row tiles only (generic_tile_h), never pooled (sumpool_supported), never 64.
+// (Of cot in {16, 32, 64}, th in {8, 16}; both tile widths always.)
+constexpr bool tiled_shape_built(bool is_float, int cot, int th, bool pool) {
+    if (is_float) return cot <= 32 && th == 16 && !pool;
+    return cot <= 32 ? !pool : (pool || th == 16);
+}
+
 // pooled-output forms exist for the streaming shapes and, in the tiled kernel, for 16-bit storage with more than 32 output channels
 inline bool sumpool_supported(int dt, int64_t Cin, int64_t N, int64_t H, int64_t W, int64_t Cout) {
     if (H % 2 || W % 2) return false;

@@ -7,8 +7,8 @@ using namespace miseg;
 extern "C" int64_t miseg_conv3x3_stats_parts(int dt, int64_t Cin, int64_t N, int64_t H, int64_t W) {
     MISEG_F16_DISPATCH_ON(dt, miseg_conv3x3_stats_parts, MISEG_BF16, Cin, N, H, W);
     if (conv_streams(dt, Cin, N, H, W)) return stream_blocks(N, H, W);
-    const int tw = tile_w(W);
-    return N * cdiv(H, generic_tile_h(dt, H, W)) * cdiv(W, tw);
+    const TiledShape t = tiled_shape(dt, H, W, 0, false);      // (the tile depends on neither Cout nor pool)
+    return N * cdiv(H, t.th) * cdiv(W, t.tw);
 }
 
 // Rows of the statistics matrix miseg_conv3x3_fwd writes for this layer (what bn_finalize must be told): one per block of the kernel
@@ -17,10 +17,9 @@ extern "C" int64_t miseg_conv3x3_fwd_parts(int dt, int64_t Cin, int64_t N, int64
     MISEG_F16_DISPATCH_ON(dt, miseg_conv3x3_fwd_parts, MISEG_BF16, Cin, N, H, W, Cout);
     const int64_t ntiles = miseg_conv3x3_stats_parts(dt, Cin, N, H, W);
     if (conv_streams(dt, Cin, N, H, W) || dt != MISEG_BF16 || !tiled_persistent()) return ntiles;
-    const int th = generic_tile_h(dt, H, W);
-    if (th != 8) return ntiles;                                                          // (launch_tiled: the persistent form serves 8-row tiles)
-    const int64_t cot = Cout <= 16 ? 16 : 32;                                           // conv3x3_fwd_impl's slice width for 8-row tiles
-    return pt_grid((int)ntiles, (int)cdiv(Cout, cot), th).blocks;
+    const TiledShape t = tiled_shape(dt, H, W, Cout, false);                            // (statistics: never a pooled output)
+    if (t.th != 8) return ntiles;                                                        // (launch_tiled: the persistent form serves 8-row tiles)
+    return pt_grid((int)ntiles, (int)cdiv(Cout, t.cot), t.th).blocks;
 }
 
 static int conv3x3_fwd_impl(void* stream, int dt, const void* in0, int64_t C0, int ups0, const void* in1, int64_t C1, int ups1,
@@ -34,35 +33,25 @@ static int conv3x3_fwd_impl(void* stream, int dt, const void* in0, int64_t C0, i
     const int vec = dt == MISEG_BF16 ? 8 : 4;
     MISEG_REQUIRE(C0 % vec == 0 && C1 % vec == 0, "conv3x3_fwd: channel counts must be multiples of %d (use conv_small for the stem)", vec);
     ConvSrc s{in0, in1, (int)C0, (int)C1, ups0, ups1};
-    const int tw = tile_w(W);
-    const int th = conv_streams(dt, C0 + C1, N, H, W) ? TH : generic_tile_h(dt, H, W);
-    const unsigned gx = (unsigned)(N * cdiv(H, th) * cdiv(W, tw));
     hipStream_t st = as_stream(stream);
     MISEG_REQUIRE(!bl.gy || (bl.coef && C1 == 0 && ups0 == 0), "conv3x3: the BatchNorm loader reads one full-resolution source");
     MISEG_REQUIRE(!br.raw || (br.saved && br.parts && !pool_out && !stats && Cout % 4 == 0), "conv3x3: epilogue reduce needs a full-resolution "
                   "output with a multiple of 4 channels and no forward statistics");
     MISEG_REQUIRE(!pool_out || (sumpool_supported(dt, C0 + C1, N, H, W, Cout) && C1 == 0 && !stats),
                   "conv3x3_fwd_sumpool: shape not supported (ask miseg_conv3x3_fwd_sumpool_supported)");
-    int cot;        // output channels per block (grid.y slices)
     if (conv_streams(dt, C0 + C1, N, H, W)) {
         // wider outputs run as 32-channel slices (grid.y): a 64-channel block would need 97 KB of LDS and the whole
         // register file, i.e. one block per CU; re-reading the (narrow) input per slice is cheaper
-        cot = Cout <= 16 ? 16 : 32;
+        const int cot = Cout <= 16 ? 16 : 32;
         // one slot layout per number of 8-channel vectors of the (<= 32) input channels; a pooled output has one source (checked above)
         const int rc = launch_conv_stream(cot, (int)((C0 + C1) / 8), C1 > 0, pool_out, (unsigned)stream_blocks(N, H, W), st, s, (int)N, (int)H, (int)W,
                                           packed_w, (int)Cout, out, stats, fin, bl, br);
         if (rc != MISEG_OK) return rc;
     } else {
-        if (dt == MISEG_BF16 && pool_out) cot = 64;
-        else if (dt == MISEG_BF16) {
-            // 8-row tiles (maps from 64^2 up) take 32 output channels per block: with 64 the weight chunk makes the block's LDS 88 KB -- one
-            // block per CU --, with 32 it is 60 KB and two fit (64^2, same box: 32->64 31.8 -> 26.7 us, 64->64 39.2 -> 36.3, 128->64 55.5 -> 49.9;
-            // the 16-row tiles of the deep layers are one block per CU either way and lose 20 % with the narrower slice)
-            cot = Cout <= 16 ? 16 : (Cout <= 32 || th == 8) ? 32 : 64;
-        } else if (dt == MISEG_F32) cot = Cout <= 16 ? 16 : 32;
-        else return fail(MISEG_E_INVALID, "conv3x3_fwd: bad dtype");
-        const int rc = launch_conv_tiled(dt, cot, tw, th, pool_out, dim3(gx, (unsigned)cdiv(Cout, cot)), st, s, (int)N, (int)H, (int)W, packed_w, (int)Cout,
-                                         out, stats, fin, bl, br);
+        const TiledShape t = tiled_shape(dt, H, W, Cout, pool_out);
+        if (!t.cot) return fail(MISEG_E_INVALID, "conv3x3_fwd: bad dtype");
+        const dim3 grid((unsigned)(N * cdiv(H, t.th) * cdiv(W, t.tw)), (unsigned)cdiv(Cout, t.cot));
+        const int rc = launch_conv_tiled(dt, t.cot, t.tw, t.th, pool_out, grid, st, s, (int)N, (int)H, (int)W, packed_w, (int)Cout, out, stats, fin, bl, br);
         if (rc != MISEG_OK) return rc;
     }
     MISEG_LAUNCH_CHECK("conv3x3_kernel");

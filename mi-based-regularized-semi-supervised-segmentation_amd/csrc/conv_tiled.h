@@ -2,6 +2,7 @@
 // storage, BatchNorm-loader and epilogue-reduce forms) and conv_tiled_f32.hip (float, every form) instantiate, each its own forms --
 // three units so that they compile side by side.
 #pragma once
+#include <type_traits>
 #include "conv.h"
 
 namespace miseg {
@@ -315,9 +316,11 @@ static int launch_tiled_bn(dim3 grid, hipStream_t st, const ConvSrc& s, int N, i
 }
 
 // Every tile shape the library is built with, as a chain of `if (the run-time shape is this one) return F<T, COT, TW, TH, POOL>(args)`:
-// what conv3x3_fwd_impl can ask for (conv_fwd.hip).  Expects cot, tw, th, pool in scope.
-#define MISEG_TILED_SHAPE(F, TT, COT, TWW, THH, POOL, ...) \
-    if (cot == COT && tw == TWW && th == THH && pool == POOL) return F<TT, COT, TWW, THH, POOL>(__VA_ARGS__);
+// the lists below name the candidates, tiled_shape_built (conv.h, beside the rule it follows from) keeps those a call can select -- a
+// shape it rejects is not instantiated and ends in the message.  Expects cot, tw, th, pool in scope.
+#define MISEG_TILED_SHAPE(F, TT, COT, TWW, THH, POOL, ...)                           \
+    if constexpr (tiled_shape_built(std::is_same<TT, float>::value, COT, THH, POOL)) \
+        if (cot == COT && tw == TWW && th == THH && pool == POOL) return F<TT, COT, TWW, THH, POOL>(__VA_ARGS__);
 #define MISEG_TILED_TILES(F, TT, COT, POOL, ...)                                                                \
     MISEG_TILED_SHAPE(F, TT, COT, 32, 8, POOL, __VA_ARGS__) MISEG_TILED_SHAPE(F, TT, COT, 32, 16, POOL, __VA_ARGS__) \
     MISEG_TILED_SHAPE(F, TT, COT, 16, 8, POOL, __VA_ARGS__) MISEG_TILED_SHAPE(F, TT, COT, 16, 16, POOL, __VA_ARGS__)

@@ -246,41 +246,46 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_pt_kernel(ConvSrc src, int
     }
 }
 
-// One tile shape in its plain forms: persistent, 8 waves, 4 waves.
+// One conv3x3_pt_kernel launch (4 waves: the persistent form serves 8-row tiles).
+template <typename TT, int COT, int TWW, int THH, bool POOL, int DEPTH>
+static void launch_conv3x3_pt_kernel(dim3 grid, hipStream_t st, const ConvSrc& s, int N, int H, int W, const void* wpk, int Cout, void* out, float* stats,
+                                     const BnFinish& fin) {
+    const size_t lb = ((size_t)(THH + 2) * (TWW + 2) + 9 * COT) * Mma<TT>::KP * sizeof(TT);
+    const int ntiles = (int)grid.x;
+    const PtGrid g = pt_grid(ntiles, (int)grid.y, THH);
+    hipFuncSetAttribute((const void*)conv3x3_pt_kernel<TT, COT, TWW, THH, POOL, 4, DEPTH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
+    hipLaunchKernelGGL((conv3x3_pt_kernel<TT, COT, TWW, THH, POOL, 4, DEPTH>), dim3((unsigned)g.blocks, grid.y), dim3(64 * 4), lb, st, s, N, H, W,
+                       (const TT*)wpk, Cout, (TT*)out, stats, fin, ntiles, g.per);
+}
+
+// One tile shape in its plain forms (every call that gets here: launch_conv_tiled hands the fused ones on).  8-row tiles: persistent
+// or 4 waves per tile; 16-row tiles: 8 waves per tile.
 template <typename TT, int COT, int TWW, int THH, bool POOL>
 static int launch_tiled(dim3 grid, hipStream_t st, const ConvSrc& s, int N, int H, int W, const void* wpk, int Cout, void* out, float* stats,
                         const BnFinish& fin, const BnLoad& bl, const BnRed& br) {
-    const size_t lb = ((size_t)(THH + 2) * (TWW + 2) + 9 * COT) * Mma<TT>::KP * sizeof(TT);
-    // the plain forms of the 8-row tiles (maps from 64^2 up: several tiles per block): persistent blocks, pipelined across tiles.
-    // Measured per launch, same box: 32-channel slices 48.1 -> 38.7 us, pooled 64-channel 75.5 -> 67.6; the
-    // 16-row tiles of the deep layers have one tile per block either way and ran 4-29 % slower in this form -> they keep the other
-    if (THH == 8 && !bl.gy && !br.raw && !fin.counter && tiled_persistent()) {
-        const int ntiles = (int)grid.x;
-        const PtGrid g = pt_grid(ntiles, (int)grid.y, THH);
-        constexpr int NWW = (THH == 16) ? 8 : 4;
-        // stages in flight ahead of the matrix cores: ONE.  Two (201 instead of 155 registers in the 32-channel-slice form) measured
-        // 6.72 / 6.73 against 6.66 / 6.63 ms per step, same box, two alternations; MISEG_CONV_DEPTH=2 selects it
-        static const int depth = [] { const char* e = getenv("MISEG_CONV_DEPTH"); return e ? atoi(e) : 1; }();
-        if (depth == 2 && !POOL) {      // (the pooled 64-channel form with two stages in flight needs 256 registers: one wave per SIMD)
-            hipFuncSetAttribute((const void*)conv3x3_pt_kernel<TT, COT, TWW, THH, POOL, NWW, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-            hipLaunchKernelGGL((conv3x3_pt_kernel<TT, COT, TWW, THH, POOL, NWW, 2>), dim3((unsigned)g.blocks, grid.y), dim3(64 * NWW), lb, st, s, N, H, W,
-                               (const TT*)wpk, Cout, (TT*)out, stats, fin, ntiles, g.per);
-        } else {
-            hipFuncSetAttribute((const void*)conv3x3_pt_kernel<TT, COT, TWW, THH, POOL, NWW, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-            hipLaunchKernelGGL((conv3x3_pt_kernel<TT, COT, TWW, THH, POOL, NWW, 1>), dim3((unsigned)g.blocks, grid.y), dim3(64 * NWW), lb, st, s, N, H, W,
-                               (const TT*)wpk, Cout, (TT*)out, stats, fin, ntiles, g.per);
-        }
-        return MISEG_OK;
-    }
-    // 16-row tiles of 16-bit layers: 8 waves (plain forms; the fused forms keep 4).  Same box, forward, us: 32^2 64->128 21.3 -> 20.6,
-    // 128->128 29.4 -> 26.5, 256->128 45.4 -> 41.9; 16^2 128->256 19.0 -> 17.8, 256->256 27.4 -> 26.3
-    if constexpr (THH == 16) {
-        if (!bl.gy && !br.raw) {        // (every call that gets here: launch_conv_tiled hands the fused ones on)
-            launch_conv3x3_kernel<TT, COT, TWW, THH, POOL, false, false, 8>(grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br);
+    if constexpr (THH == 8) {
+        // the plain forms of the 8-row tiles (maps from 64^2 up: several tiles per block): persistent blocks, pipelined across tiles.
+        // Measured per launch, same box: 32-channel slices 48.1 -> 38.7 us, pooled 64-channel 75.5 -> 67.6; the
+        // 16-row tiles of the deep layers have one tile per block either way and ran 4-29 % slower in this form -> they keep the other
+        if (!bl.gy && !br.raw && !fin.counter && tiled_persistent()) {
+            // stages in flight ahead of the matrix cores: ONE.  Two (201 instead of 155 registers in the 32-channel-slice form) measured
+            // 6.72 / 6.73 against 6.66 / 6.63 ms per step, same box, two alternations; MISEG_CONV_DEPTH=2 selects it
+            if constexpr (!POOL) {      // (the pooled 64-channel form with two stages in flight needs 256 registers: one wave per SIMD)
+                static const int depth = [] { const char* e = getenv("MISEG_CONV_DEPTH"); return e ? atoi(e) : 1; }();
+                if (depth == 2) {
+                    launch_conv3x3_pt_kernel<TT, COT, TWW, THH, POOL, 2>(grid, st, s, N, H, W, wpk, Cout, out, stats, fin);
+                    return MISEG_OK;
+                }
+            }
+            launch_conv3x3_pt_kernel<TT, COT, TWW, THH, POOL, 1>(grid, st, s, N, H, W, wpk, Cout, out, stats, fin);
             return MISEG_OK;
         }
+        launch_conv3x3_kernel<TT, COT, TWW, THH, POOL, false, false, 4>(grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br);
+    } else {
+        // 16-row tiles of 16-bit layers: 8 waves (plain forms; the fused forms keep 4).  Same box, forward, us: 32^2 64->128 21.3 -> 20.6,
+        // 128->128 29.4 -> 26.5, 256->128 45.4 -> 41.9; 16^2 128->256 19.0 -> 17.8, 256->256 27.4 -> 26.3
+        launch_conv3x3_kernel<TT, COT, TWW, THH, POOL, false, false, 8>(grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br);
     }
-    launch_conv3x3_kernel<TT, COT, TWW, THH, POOL, false, false, 4>(grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br);
     return MISEG_OK;
 }
 
@@ -290,6 +295,7 @@ int launch_conv_tiled(int dt, int cot, int tw, int th, bool pool, dim3 grid, hip
     if (dt == MISEG_F32) return launch_conv_tiled_f32(cot, tw, th, pool, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br);
 #endif
     if (bl.gy || br.raw) return launch_conv_tiled_bn(cot, tw, th, pool, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br);
+    // not built (tiled_shape_built): 64-channel slices of 8-row tiles, not pooled -- tiled_shape gives an 8-row tile 32
     MISEG_TILED_SELECT_16BIT(launch_tiled, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br)
 }
 

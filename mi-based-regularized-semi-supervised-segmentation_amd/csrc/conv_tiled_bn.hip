@@ -6,6 +6,7 @@ namespace miseg {
 
 int launch_conv_tiled_bn(int cot, int tw, int th, bool pool, dim3 grid, hipStream_t st, const ConvSrc& s, int N, int H, int W, const void* wpk,
                          int Cout, void* out, float* stats, const BnFinish& fin, const BnLoad& bl, const BnRed& br) {
+    // not built (tiled_shape_built): 64-channel slices of 8-row tiles, not pooled -- tiled_shape gives an 8-row tile 32
     MISEG_TILED_SELECT_16BIT(launch_tiled_bn, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br)
 }
 

@@ -14,6 +14,7 @@ static int launch_tiled_f32(dim3 grid, hipStream_t st, const ConvSrc& s, int N, 
 
 int launch_conv_tiled_f32(int cot, int tw, int th, bool pool, dim3 grid, hipStream_t st, const ConvSrc& s, int N, int H, int W, const void* wpk,
                           int Cout, void* out, float* stats, const BnFinish& fin, const BnLoad& bl, const BnRed& br) {
+    // not built (tiled_shape_built): 8-row tiles -- generic_tile_h gives float 16 rows at every size
     MISEG_TILED_SELECT_F32(launch_tiled_f32, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br)
 }
 

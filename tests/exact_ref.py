@@ -179,6 +179,30 @@ def conv_streams(dtype, cin, n, h, w) -> bool:
     return dtype in HALF and cin <= 32 and w >= 32 and n * ((h + 15) // 16) * ((w + 31) // 32) >= 512
 
 
+def tiled_shape(dtype, h, w, cout, pool=False):
+    """csrc/conv.h tiled_shape(): (output channels per block, tile width, tile height) of a call the tiled kernel serves."""
+    tw = 32 if w >= 32 else 16
+    th = 8 if dtype in HALF and h * w >= 64 * 64 else 16
+    if dtype in HALF:
+        cot = 64 if pool else 16 if cout <= 16 else 32 if cout <= 32 or th == 8 else 64
+    else:
+        cot = 16 if cout <= 16 else 32
+    return cot, tw, th
+
+
+def fwd_parts(dtype, cin, n, h, w, cout, persistent=True):
+    """csrc/conv_fwd.hip miseg_conv3x3_fwd_parts() for a call the tiled kernel serves: one statistics row per tile, or -- 16-bit 8-row
+    tiles in the persistent form (conv.h pt_grid(): two blocks per CU over the output-channel slices) -- one per persistent block."""
+    assert not conv_streams(dtype, cin, n, h, w)
+    cot, tw, th = tiled_shape(dtype, h, w, cout)
+    ntiles = n * ((h + th - 1) // th) * ((w + tw - 1) // tw)
+    if th != 8 or not persistent:
+        return ntiles
+    target = max(1, 512 // ((cout + cot - 1) // cot))
+    per = max(1, (ntiles + target - 1) // target)
+    return (ntiles + per - 1) // per
+
+
 def wgrad_splits(n, h, w, cin, cout):
     """csrc/conv_wgrad.hip wgrad_splits(): (8 x 32 tiles, blocks per split, splits)."""
     ntiles = n * ((h + 7) // 8) * ((w + 31) // 32)
@@ -214,6 +238,15 @@ FWD_CASES = {
     "tiled_up_32_16": (3, 20, 36, 32, 1, 0, 0, 16, 2, 1, ALL),
     "stream_up_16_cat_16_16": (4, 256, 256, 16, 1, 16, 0, 16, 2, 1, HALF),
     "tiled_up_16_cat_16_16": (3, 20, 36, 16, 1, 16, 0, 16, 2, 1, ALL),
+    # one case per tile shape the library is built with and no case above selects (tiled_shape: channels per block, tile width x height;
+    # fp32 always has 16-row tiles and at most 32 channels per block); Cin = 64: two channel chunks per tile, once per tile height
+    "t16x16_8_8": (2, 16, 16, 8, 0, 0, 0, 8, 2, 1, ALL),                        # 16, 16 x 16; half a channel slice
+    "t16x16_ragged_16_32": (2, 20, 20, 16, 0, 0, 0, 32, 2, 1, ALL),             # 32, 16 x 16
+    "t16x16_ragged_64_64": (1, 20, 20, 64, 0, 0, 0, 64, 2, 1, ALL),             # 64, 16 x 16
+    "t8x32_16_16": (2, 64, 64, 16, 0, 0, 0, 16, 2, 1, ALL),                     # 16-bit: 16, 32 x 8
+    "t8x32_ragged_8_32": (2, 70, 66, 8, 0, 0, 0, 32, 2, 1, ALL),                # 16-bit: 32, 32 x 8 with edge tiles
+    "t8x16_16_16": (1, 256, 16, 16, 0, 0, 0, 16, 2, 1, ALL),                    # 16-bit: 16, 16 x 8
+    "t8x16_ragged_64_64": (2, 258, 18, 64, 0, 0, 0, 64, 2, 1, ALL),             # 16-bit: 32, 16 x 8, two slices
 }
 
 
@@ -233,6 +266,13 @@ STATS_CASES = {
     "stream_16_16": (4, 256, 256, 16, 16, ALL),
     "tiled_ragged_8_32": (3, 20, 36, 8, 32, ALL),
     "pt_remainder_64_64": (3, 100, 200, 64, 64, ALL),   # 16-bit: the persistent tiled kernel, one row per block of two tiles
+    # the other tile shapes (FWD_CASES has the map from size to shape)
+    "t16x16_8_8": (2, 16, 16, 8, 8, ALL),
+    "t16x16_ragged_16_32": (2, 20, 20, 16, 32, ALL),
+    "t16x16_ragged_16_64": (1, 20, 20, 16, 64, ALL),
+    "t8x32_16_16": (2, 64, 64, 16, 16, ALL),
+    "t8x16_16_16": (1, 256, 16, 16, 16, ALL),
+    "t8x16_ragged_64_64": (2, 258, 18, 64, 64, ALL),
 }
 
 
@@ -286,6 +326,8 @@ SUMPOOL_CASES = {
     "stream_ragged_16_32": (6, 250, 230, 16, 32, True),
     "tiled_64_64": (3, 20, 36, 64, 64, False),          # the tiled kernel's 64-channel-slice form (Cs > 32), 16-row tiles
     "tiled8_128_64": (2, 64, 70, 128, 64, False),       # ... 8-row tiles, ragged width
+    "tiled16x16_ragged_64_64": (2, 20, 20, 64, 64, False),      # ... 16-wide 16-row tiles
+    "tiled8x16_ragged_16_64": (1, 258, 18, 16, 64, False),      # ... 16-wide 8-row tiles
 }
 
 
@@ -400,6 +442,17 @@ DGRAD_BN_CASES = {
     "eval_stream_32_16": (4, 256, 256, 32, 16, False, HALF),
     "train_tiled": (1, 16, 64, 16, 16, True, ALL),
     "train_tiled_rows": (1, 32, 32, 16, 16, True, ALL),
+    # the fused forms on every tile shape (Cs decides the channels per block; FWD_CASES has the map from size to shape).  pool_*: even
+    # sizes and Cs = 64, so that 16-bit storage also has the pooled form (64 channels per block on that tile)
+    "eval_t16x16_16_16": (2, 16, 16, 16, 16, False, ALL),
+    "eval_t16x16_ragged_16_32": (2, 20, 20, 16, 32, False, ALL),
+    "eval_pool_t16x16_64_64": (1, 16, 16, 64, 64, False, ALL),
+    "eval_t16x32_8_32": (2, 32, 32, 8, 32, False, ALL),
+    "eval_pool_t16x32_ragged_16_64": (1, 36, 40, 16, 64, False, ALL),
+    "eval_t8x32_64_16": (1, 64, 64, 64, 16, False, ALL),
+    "eval_pool_t8x32_ragged_8_64": (1, 70, 66, 8, 64, False, ALL),
+    "eval_t8x16_16_16": (1, 256, 16, 16, 16, False, ALL),
+    "eval_pool_t8x16_ragged_16_64": (1, 258, 18, 16, 64, False, ALL),
 }
 
 
@@ -483,6 +536,26 @@ def dgrad_bn_reference(name: str, dtype):
     assert_exact_range(gx, torch.float32, abs_sum, quantum=q)       # the fp32 accumulator holds every partial sum
     round_to(gx, dtype)
     return dict(bn=bn, coef=coef, graw_loaded=graw, gx=gx, quantum=q)
+
+
+def dgrad_red_reference(name: str, dtype):
+    """The epilogue reduce of miseg_conv3x3_dgrad_bn (csrc/conv_tiled.h, RED) for an evaluation-mode DGRAD_BN_CASES entry: the layer
+    that produced the Cs-channel tensor whose gradient the launch writes has raw output `raw` and coefficients `saved`; the epilogue
+    takes dz = [raw * scale + shift > 0] * (the gradient AS STORED) and sums dz and dz * xhat per channel.  Everything is a multiple of
+    the gradient's quantum / 2 (invstd >= 1/2), and the whole-tensor absolute sums are asserted below 2^24 of it: any partition is exact.
+    -> dict(raw, saved, gbeta, ggamma)."""
+    n, h, w, k, cs, training, _ = DGRAD_BN_CASES[name]
+    assert not training         # (training mode: the gradient is a multiple of 2^-10, whole-tensor sums would leave fp32's exact range)
+    ref = dgrad_bn_reference(name, dtype)
+    raw = ints(f"dgbn/{name}/red/raw", (n, cs, h, w), -2, 2)
+    _, saved = make_saved(f"dgbn/{name}/red", cs)
+    v = lambda r: saved[r].view(1, -1, 1, 1)
+    dz = (raw * v(2) + v(3) > 0).to(F64) * round_to(ref["gx"], dtype)
+    dev = dz * (raw - v(0))
+    q = ref["quantum"]
+    assert_exact_range(dz.sum((0, 2, 3)), torch.float32, dz.abs().sum((0, 2, 3)).max(), quantum=q)
+    assert_exact_range(dev.sum((0, 2, 3)), torch.float32, dev.abs().sum((0, 2, 3)).max(), quantum=q)
+    return dict(raw=raw, saved=saved, gbeta=dz.sum((0, 2, 3)), ggamma=dev.sum((0, 2, 3)) * saved[1])
 
 
 # ---- recipes of the remaining GPU tests (kept here so that test_cpu_exact_ref.py proves them in range too)

@@ -219,6 +219,31 @@ def test_fused_batchnorm_data_gradient_recipes_are_in_range(name):
         ref = R.dgrad_bn_reference(name, dtype)
         if not R.DGRAD_BN_CASES[name][5]:
             assert ref["quantum"] >= 0.25 and torch.equal(ref["graw_loaded"], ref["bn"]["graw"])      # eval mode: nothing to round
+            if "stream" not in name:
+                R.dgrad_red_reference(name, dtype)          # (asserts the range of the epilogue reduce's sums)
+    n, h, w, k, cs = R.DGRAD_BN_CASES[name][:5]
+    assert R.conv_streams(torch.bfloat16, k, n, h, w) == ("stream" in name) and ("pool_" not in name or (cs > 32 and h % 2 == 0 and w % 2 == 0))
+
+
+def test_every_built_tile_shape_has_a_case():
+    """The tiled kernel is built with the shapes csrc/conv.h tiled_shape() can return and no others (tiled_shape_built): 14 for 16-bit
+    storage, 4 for fp32.  A shape that went missing is a run-time error, so each one is selected by a plain case (forward, statistics or
+    pooled table) and by a fused case (DGRAD_BN_CASES).  Shape = (fp32, channels per block, tile width, tile height, pooled)."""
+    built = {(False, cot, tw, th, False) for cot in (16, 32) for tw in (16, 32) for th in (8, 16)}
+    built |= {(False, 64, tw, 16, False) for tw in (16, 32)} | {(False, 64, tw, th, True) for tw in (16, 32) for th in (8, 16)}
+    built |= {(True, cot, tw, 16, False) for cot in (16, 32) for tw in (16, 32)}
+    shape = lambda d, h, w, cout, pool=False: (d == torch.float32,) + R.tiled_shape(d, h, w, cout, pool) + (pool,)
+    plain, fused = set(), set()
+    for n, h, w, c0, _, c1, _, cout, _, _, types in R.FWD_CASES.values():
+        plain |= {shape(d, h, w, cout) for d in types if not R.conv_streams(d, c0 + c1, n, h, w)}
+    for n, h, w, cin, cout, types in R.STATS_CASES.values():
+        plain |= {shape(d, h, w, cout) for d in types if not R.conv_streams(d, cin, n, h, w)}
+    for n, h, w, k, cs, _ in R.SUMPOOL_CASES.values():
+        plain |= {shape(d, h, w, cs, True) for d in R.HALF if not R.conv_streams(d, k, n, h, w)}
+    for name, (n, h, w, k, cs, _, types) in R.DGRAD_BN_CASES.items():
+        fused |= {shape(d, h, w, cs) for d in types if not R.conv_streams(d, k, n, h, w)}
+        fused |= {shape(d, h, w, cs, True) for d in types if "pool_" in name and d in R.HALF}
+    assert plain == built and fused == built
 
 
 def test_mover_loader_and_forward_recipes_are_in_range():

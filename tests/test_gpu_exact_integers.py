@@ -11,6 +11,16 @@ Case -> kernel (csrc/conv_*.hip, csrc/bn.hip; the dispatch predicates are mirror
 own queries).  16-bit = bf16 and, through the -DMISEG_F16_BUILD twins, IEEE half.
   tiled_* / deep_* (H * W < 64^2)            conv3x3_kernel: 16-row tiles, 16 / 32 / 64-channel slices, 16-wide tiles at W < 32; fp32 always
   pt_remainder_64_64 (16-bit, 100 x 200)     conv3x3_pt_kernel: 8-row tiles, 273 tiles over 137 persistent blocks
+  t16x16_* / t8x32_* / t8x16_* (and t16x32 in the fused table): one case per tile shape the library is built with (csrc/conv.h
+                                             tiled_shape_built) that no case above selects.  Channels per block, tile width x height:
+                                             16-bit  t16x16 (16 x 16, 20 x 20)   16 | 32 | 64, 16 x 16    conv3x3_kernel, 8 waves
+                                                     t8x32 (64 x 64, 70 x 66)    16 | 32, 32 x 8          conv3x3_pt_kernel
+                                                     t8x16 (256 x 16, 258 x 18)  16 | 32, 16 x 8          conv3x3_pt_kernel
+                                             fp32    every size                  16 | 32, 16 | 32 x 16    conv3x3_kernel, 4 waves
+                                             pooled (16-bit, Cs = 64): 64 on all four tiles (16-row: conv3x3_kernel, 8 waves; 8-row:
+                                             conv3x3_pt_kernel)
+  test_eight_row_tiles_under_the_conv_switches  MISEG_CONV_PERSISTENT=0: conv3x3_kernel, 4 waves, on the 8-row shapes (pooled too);
+                                             MISEG_CONV_DEPTH=2: conv3x3_pt_kernel<.., DEPTH = 2> (not pooled); a fresh process each
   stream_* (16-bit, Cin <= 32, >= 512 tiles) conv3x3_stream_kernel: NV = 1..4, concat (DU) and upsampled loaders, ragged 250 x 230
   test_data_gradient / _concat_in_one_launch the same three kernels behind pack kind 1, channel slices, two destinations (C1 = 4, 16)
   test_pooled_data_gradient                  stream kernel POOL (+ accumulate), conv3x3_kernel POOL 64 slices, conv3x3_pt_kernel POOL
@@ -24,12 +34,18 @@ own queries).  16-bit = bf16 and, through the -DMISEG_F16_BUILD twins, IEEE half
   test_bn_relu_forward                       bn_relu_fwd_pool_kernel (C / vector a power of two <= 32), bn_relu_fwd_kernel<POOL>
   test_bn_relu_backward                      bn_relu_bwd_reduce_kernel / bn_bwd_apply_kernel <POOL = 0 | 1> (+ gy2, + ACC),
                                              bn_bwd_finalize_kernel, the last-block finish (_sync)
-  test_batchnorm_backward_folded_...         reduce + finalize -> bwd_coef; the BNL loaders of conv3x3_kernel and conv3x3_stream_kernel
+  test_batchnorm_backward_folded_...         reduce + finalize -> bwd_coef; the BNL loaders of conv3x3_kernel and conv3x3_stream_kernel;
+                                             evaluation-mode tiled cases: conv3x3_kernel<.., BNL, RED> in its forms BNL, RED and BNL + RED
+                                             (4 waves) on every tile shape of 16-bit storage and of fp32, pool_* (16-bit): POOL + BNL
   test_batchnorm_loaders_with_nonzero_...    the BNL loaders of the stream, tiled and all three weight-gradient kernels with P, Q != 0
-Not covered here: miseg_bn_relu_bwd_ext and the red_* epilogue of miseg_conv3x3_dgrad_bn (their sums are the ones checked above, taken
-in another kernel's epilogue), and everything that derives invstd through rsqrtf in a kernel (miseg_bn_finalize, miseg_bn_relu_fwd_acc,
-miseg_conv3x3_bn_fwd): not exact by design.
+Not covered here: miseg_bn_relu_bwd_ext, the red_* epilogue of miseg_conv3x3_dgrad_bn on the streaming kernel and in training mode
+(their sums are the ones checked above, taken in another kernel's epilogue), and everything that derives invstd through rsqrtf in a
+kernel (miseg_bn_finalize, miseg_bn_relu_fwd_acc, miseg_conv3x3_bn_fwd): not exact by design.
 """
+import os
+import subprocess
+import sys
+
 import pytest
 import torch
 
@@ -39,6 +55,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 F64 = torch.float64
 NAN = float("nan")
+# the library's own reading of the switch (csrc/conv.h tiled_persistent()): unset in the suite, set in the children of the last test
+PERSISTENT = int(os.environ.get("MISEG_CONV_PERSISTENT", "1") or 0) != 0
 
 
 def _abi():
@@ -129,13 +147,14 @@ def test_forward_convolution(name, dtype):
     parts = c.query("miseg_conv3x3_stats_parts", dt, cin, n, h, w)
     if name.startswith("stream") and dtype != torch.float32:            # the streaming kernel: one row per persistent block
         assert parts == min(n * cdiv(h, 16) * cdiv(w, 32), 512)
-    elif dtype != torch.float32 and h * w >= 64 * 64:                   # 8-row tiles
-        assert parts == n * cdiv(h, 8) * cdiv(w, 32)
-        if name.startswith("pt_"):                                     # ... in the persistent form: fewer blocks than tiles, not a divisor
-            blocks = c.query("miseg_conv3x3_fwd_parts", dt, cin, n, h, w, cout)
+    else:                                                               # one tile per row, of the shape the selection rule gives
+        _, tw, th = R.tiled_shape(dtype, h, w, cout)
+        assert th == (8 if dtype != torch.float32 and h * w >= 64 * 64 else 16) and tw == (32 if w >= 32 else 16)
+        assert parts == n * cdiv(h, th) * cdiv(w, tw)
+        blocks = c.query("miseg_conv3x3_fwd_parts", dt, cin, n, h, w, cout)
+        assert blocks == R.fwd_parts(dtype, cin, n, h, w, cout, PERSISTENT)
+        if name.startswith("pt_") and th == 8 and PERSISTENT:          # the persistent form: fewer blocks than tiles, not a divisor
             assert blocks < parts and parts % blocks != 0
-    else:
-        assert parts == n * cdiv(h, 16) * cdiv(w, 32 if w >= 32 else 16)
     out = nans((n, h, w, cout), dtype)
     xd0, xd1 = dev(x0, dtype), dev(x1, dtype)
     c.call("miseg_conv3x3_fwd", st(), dt, ptr(xd0), c0, ups0, ptr(xd1), c1, ups1, n, h, w, ptr(pack(wt, dtype)), cout, ptr(out), None)
@@ -154,7 +173,9 @@ def test_forward_convolution_batchnorm_statistics(name, dtype):
     dt = DT(dtype)
     xd, pk = dev(x, dtype), pack(wt, dtype)
     parts = c.query("miseg_conv3x3_fwd_parts", dt, cin, n, h, w, cout)
-    if name.startswith("pt_") and dtype != torch.float32:
+    if not R.conv_streams(dtype, cin, n, h, w):
+        assert parts == R.fwd_parts(dtype, cin, n, h, w, cout, PERSISTENT)
+    if name.startswith("pt_") and dtype != torch.float32 and PERSISTENT:
         assert parts < c.query("miseg_conv3x3_stats_parts", dt, cin, n, h, w)
     out, stats = nans((n, h, w, cout), dtype), nans((parts, 2, cout), torch.float32)
     c.call("miseg_conv3x3_fwd", st(), dt, ptr(xd), cin, 0, None, 0, 0, n, h, w, ptr(pk), cout, ptr(out), ptr(stats))
@@ -545,3 +566,63 @@ def test_batchnorm_backward_folded_into_the_data_gradient(name, dtype):
     out = nans((n, h, w, cs), dtype)
     c.call("miseg_conv3x3_dgrad_bn", st(), dt, ptr(dev(ref["graw_loaded"], dtype)), None, None, k, n, h, w, ptr(pk), cs, ptr(out), 0, None, None, None)
     assert torch.equal(host(out), want)
+    if "pool_" in name and dtype != torch.float32:      # the loader in front of the 2 x 2 sum-pooled epilogue: four exact fp32 sums, one rounding
+        assert c.query("miseg_conv3x3_dgrad_bn_supported", dt, k, n, h, w, cs, 1)
+        out = nans((n, h // 2, w // 2, cs), dtype)
+        c.call("miseg_conv3x3_dgrad_bn", st(), dt, ptr(rawd), ptr(gyd), ptr(coef), k, n, h, w, ptr(pk), cs, ptr(out), 1, None, None, None)
+        assert torch.equal(host(out), R.round_to(R.dgrad_ref(ref["graw_loaded"], case["w"])["pooled"], dtype))
+    if training or "stream" in name:
+        return
+    # the epilogue reduce (evaluation-mode tiled cases: exact_ref.dgrad_red_reference), alone on the plain tensor and behind the loader:
+    # the same gradient, and partial rows that add up to the exact sums of dz and dz * xhat of the layer that produced the Cs-channel tensor
+    red = R.dgrad_red_reference(name, dtype)
+    rows = c.query("miseg_conv3x3_dgrad_red_parts", dt, k, n, h, w, cs)
+    _, tw, th = R.tiled_shape(dtype, h, w, cs)
+    assert rows == n * cdiv(h, th) * cdiv(w, tw)
+    rraw, rsaved = dev(red["raw"], dtype), f32(red["saved"])
+    for src, gy_, coef_ in ((dev(ref["graw_loaded"], dtype), None, None), (rawd, gyd, coef)):
+        out, parts = nans((n, h, w, cs), dtype), nans((rows, 2, cs), torch.float32)
+        c.call("miseg_conv3x3_dgrad_bn", st(), dt, ptr(src), ptr(gy_), ptr(coef_), k, n, h, w, ptr(pk), cs, ptr(out), 0, ptr(rraw), ptr(rsaved), ptr(parts))
+        assert torch.equal(host(out), want)
+        tot = parts.cpu().to(F64).sum(0)
+        assert torch.equal(tot[0], red["gbeta"]) and torch.equal(tot[1], red["ggamma"])
+
+
+# =================================================================================================================== f. the switches
+def _eight_row_cases():
+    """The 16-bit cases of the forward, statistics and pooled tables that the tiled kernel serves with 8-row tiles."""
+    eight = lambda d, cin, n, h, w, cout: not R.conv_streams(d, cin, n, h, w) and R.tiled_shape(d, h, w, cout)[2] == 8
+    fwd = [(k, d) for k, v in sorted(R.FWD_CASES.items()) for d in v[-1] if d in R.HALF and eight(d, v[3] + v[5], v[0], v[1], v[2], v[7])]
+    stats = [(k, d) for k, v in sorted(R.STATS_CASES.items()) for d in v[-1] if d in R.HALF and eight(d, v[3], v[0], v[1], v[2], v[4])]
+    pooled = [(k, d) for k, v in sorted(R.SUMPOOL_CASES.items()) for d in R.HALF if eight(d, v[3], v[0], v[1], v[2], v[4])]
+    return fwd, stats, pooled
+
+
+def _switch_child():
+    """Runs in a fresh process (the library reads its switches once): the 8-row cases through the test functions above."""
+    fwd, stats, pooled = _eight_row_cases()
+    for fn, cases in ((test_forward_convolution, fwd), (test_forward_convolution_batchnorm_statistics, stats), (test_pooled_data_gradient, pooled)):
+        for name, dtype in cases:
+            fn(name, dtype)
+            torch.cuda.synchronize()
+            _LIVE.clear()
+    print(f"switch child ok: {len(fwd)} forward, {len(stats)} statistics, {len(pooled)} pooled cases")
+
+
+CHILD = "import conftest, test_gpu_exact_integers as t; t._switch_child()"       # conftest: the import paths of the suite
+
+
+def test_eight_row_tiles_under_the_conv_switches():
+    """MISEG_CONV_PERSISTENT=0 (the 4-wave per-tile forms of the 8-row tiles) and MISEG_CONV_DEPTH=2 (two stages in flight in the
+    persistent form, non-pooled): each in a fresh process, one after the other, the second only if the first passed; every 8-row
+    forward, statistics and pooled case against the same float64 references, equality at every element."""
+    fwd, stats, pooled = _eight_row_cases()
+    shapes = {R.tiled_shape(d, *R.FWD_CASES[k][1:3], R.FWD_CASES[k][7])[:2] for k, d in fwd}
+    assert shapes == {(16, 16), (16, 32), (32, 16), (32, 32)} and stats and len(pooled) >= 4       # both slice widths on both tile widths
+    for switch in ("MISEG_CONV_PERSISTENT=0", "MISEG_CONV_DEPTH=2"):
+        key, value = switch.split("=")
+        env = {k: v for k, v in os.environ.items() if k not in ("MISEG_CONV_PERSISTENT", "MISEG_CONV_DEPTH")}
+        env[key] = value
+        res = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", CHILD], env=env,
+                             cwd=os.path.dirname(os.path.abspath(__file__)), capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0 and "switch child ok" in res.stdout, switch + "\n" + res.stdout[-2000:] + res.stderr[-4000:]
