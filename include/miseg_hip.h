@@ -310,7 +310,9 @@ int miseg_head_global_var_bwd(void* stream, int dt, int64_t B, int64_t H, int64_
  *              (semi_seg/epocher.py:165-166) with the one-hot of class2one_hot
  *              (whl:deepclustering2/utils/general.py:221-235) taken from int64 labels [N,H,W]:
  *              loss = mean_{n,h,w} sum_c -t*log((p+1e-16)/(t+1e-16)); glogits = upstream * d/dlogits.
- *              A label outside [0,C) sets *bad_label (int32) != 0 (the reference asserts).
+ *              A label outside [0,C) (the reference asserts in class2one_hot) sets *bad_label (int32, never cleared here: the
+ *              caller zeroes it) != 0; that pixel adds 0 to the loss, the divisor stays N*H*W, and its C entries of glogits
+ *              are written as 0 (library version 411; before, they were left unwritten).
  * softmax_mse: ref semi_seg/epocher.py:221-224 -- mean((softmax(a) - softmax(flip(b)))^2) over all
  *              elements, b detached; flip(b) per `flips` is index math.  ga = upstream * d/da.
  * softmax_klcons: the `UDARegCriterion.name: kl` form of the same term (ref semi_seg/trainer.py:137,194 with

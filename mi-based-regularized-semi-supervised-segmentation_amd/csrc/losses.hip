@@ -18,6 +18,11 @@ __device__ __forceinline__ void softmax_c(const float* __restrict__ z, int C, fl
     for (int c = 0; c < C; ++c) p[c] = p[c] / s;
 }
 
+// The gradient row of a pixel whose label is out of range.  Out of line on purpose: with these stores inside softmax_kl_kernel's
+// branch the compiler laid the loop out differently and contracted two additions of the VALID path into FMAs -- the gradient moved in
+// its last bit, and a training run (whose BatchNorm-shadowed biases follow rounding noise) no longer reproduced the earlier builds'.
+__device__ __noinline__ void zero_row(float* __restrict__ g, int C) { for (int c = 0; c < C; ++c) g[c] = 0.f; }
+
 // KL_div(softmax(logits), onehot(labels)), mean over pixels (whl:loss/kl_losses.py:113-126)
 template <int C>
 __global__ __launch_bounds__(kLT) void softmax_kl_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
@@ -34,7 +39,7 @@ __global__ __launch_bounds__(kLT) void softmax_kl_kernel(const float* __restrict
         for (int c = 0; c < C; ++c) z[c] = logits[i * C + c];
         softmax_c(z, C, p);
         const int64_t t = labels[i];
-        if (t < 0 || t >= C) { *bad = 1; continue; }
+        if (t < 0 || t >= C) { *bad = 1; if (glogits) zero_row(glogits + i * C, C); continue; }
         float kl = 0.f, pt = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) {

@@ -841,7 +841,7 @@ def _logits_nhwc(t: Tensor) -> Tensor:
 
 class _SoftmaxKL(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits: Tensor, labels: Tensor):
+    def forward(ctx, logits: Tensor, labels: Tensor, flag_box: list):
         _need_gpu(logits, labels)
         raw_logits = logits
         logits = _logits_nhwc(logits)
@@ -857,19 +857,31 @@ class _SoftmaxKL(torch.autograd.Function):
         call("miseg_softmax_kl", _stream(), _ptr(logits), _ptr(labels), n, h, w, c, None, _ptr(loss), _ptr(glogits), _ptr(bad),
              _ptr(ws), ws.numel())
         ctx.save_for_backward(glogits)
-        ctx.bad = bad
         ctx.part = _split_part_of(raw_logits, logits)
+        flag_box.append(bad)      # the bad-label flag, handed to softmax_kl beside the graph (a second output would cost the backward a zeros launch)
         return loss
 
     @staticmethod
     def backward(ctx, g: Tensor):
         (glogits,) = ctx.saved_tensors
-        return _scaled_grad(ctx.part, glogits, g), None
+        return _scaled_grad(ctx.part, glogits, g), None, None
 
 
 def softmax_kl(logits: Tensor, labels: Tensor, check_labels: bool = True) -> Tensor:
-    """KL_div(softmax(logits), class2one_hot(labels)) with reduction='mean'."""
-    return _SoftmaxKL.apply(logits, labels)
+    """KL_div(softmax(logits), class2one_hot(labels)) with reduction='mean'.  A label outside [0, C) -- an ignore index, a mask with
+    more classes than the configuration -- makes the reference's ``class2one_hot`` raise AssertionError; the kernel flags it (such a
+    pixel adds nothing to the loss and gets a zero gradient) and, with ``check_labels``, the flag goes to ``checks.require_zero``:
+    raised here outside a ``checks.deferred`` block (one host read, as the evaluation epochers do: they read the loss right after
+    anyway), and at the iteration's fetch inside one (the train step: the flag is one of the iteration's int32 counters and travels with
+    its report -- no launch, no synchronisation)."""
+    flag_box: list = []
+    loss = _SoftmaxKL.apply(logits, labels, flag_box)
+    bad = flag_box[0]
+    if check_labels:
+        from . import checks
+        checks.require_zero(bad, AssertionError, f"softmax_kl: a label lies outside [0, {int(logits.shape[1])}) "
+                                                 f"(class2one_hot of the {int(logits.shape[1])}-class configuration would refuse it)")
+    return loss
 
 
 class _SoftmaxMSE(torch.autograd.Function):

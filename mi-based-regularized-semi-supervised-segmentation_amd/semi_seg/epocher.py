@@ -182,7 +182,9 @@ class _Pending:
 
 
 class EvalEpocher(_num_class_mixin, _Epocher):
-    """Per-patient evaluation: KL loss + 3D Dice (ref :36-73)."""
+    """Per-patient evaluation: KL loss + 3D Dice (ref :36-73).  A label outside [0, C) raises AssertionError at once, batch by batch
+    (``ops.softmax_kl`` outside a ``checks.deferred`` block reads its flag where the loss is read anyway), as the reference's
+    ``class2one_hot`` does; the inference epocher inherits this."""
 
     def __init__(self, model, val_loader: T_loader, sup_criterion: T_loss, cur_epoch=0, device="cpu") -> None:
         super().__init__(model, num_batches=len(val_loader), cur_epoch=cur_epoch, device=device)
