@@ -670,7 +670,7 @@ int miseg_augment_slices(void* stream, const uint8_t* atlas_img, const uint8_t* 
                          int64_t out_w, float* img_out, int64_t* gt_out);
 
 /* ------------------------------------------------------------------------------------------
- * Contrastive encoder pre-training (Trainer.name=contrast; csrc/contrast.hip)
+ * Contrastive encoder pre-training (Trainer.name=contrast; csrc/supcon.hip, csrc/contrast.hip)
  * supcon : ref contrastyou/epocher/contrast_epocher.py:90-95 -- F.normalize(e, dim=1), chunk into views, stack, and
  *          contrastyou/losses/contrast_loss.py:21-100 SupConLoss(contrast_mode='all') -- in one call, with the gradient with respect
  *          to the RAW embeddings.  e fp32 [N][D] row-major, N = V*B view-major (rows v*B .. v*B+B-1 are view v); labels int32[B]

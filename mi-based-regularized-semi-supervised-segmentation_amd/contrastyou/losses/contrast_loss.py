@@ -3,7 +3,7 @@ ref ``contrastyou/losses/contrast_loss.py:11-100``: ``SupConLoss(temperature, co
 ``forward(features [bsz, n_views, ...], labels=None, mask=None)``.
 
 Two paths.  ``contrast_mode='all'`` without an explicit ``mask`` on the GPU runs ONE library call (``miseg_amd.ops.supcon``,
-csrc/contrast.hip: normalisation, loss and the gradient, deterministic); everything else -- ``'one'``, an explicit (possibly asymmetric)
+csrc/supcon.hip: normalisation, loss and the gradient, deterministic); everything else -- ``'one'``, an explicit (possibly asymmetric)
 ``mask``, CPU tensors, a shape outside ``ops.supcon_supported`` -- is composed from torch operations below.
 
 The kernel L2-normalises its rows.  The pre-training epocher hands it the projector's RAW output through ``from_embeddings`` (the

@@ -7,7 +7,7 @@ of a head run in ONE fused launch.  ``forward(features)`` keeps the reference si
 list of per-sub-head probabilities; ``forward_gathered(features, src, flips)`` additionally fuses the
 epocher's sample gather / flip replay / cat (semi_seg/epocher.py:258-273) into the same kernel.
 ``head_type='linear'`` with ``normalize=False`` (the shipped config, config/semi.yaml:45-55) runs on the tuned
-kernels of csrc/heads_*.hip / mi_global.hip; ``head_type='mlp'`` and ``normalize=True`` (ref :106-126, :146-161) run on the
+kernels of csrc/heads_*.hip / heads_global.hip; ``head_type='mlp'`` and ``normalize=True`` (ref :106-126, :146-161) run on the
 generic fused kernels of csrc/heads_var.hip (same gather / flip fusion, forward recomputed in the backward).
 
 ``ProjectionHead`` (contrastive pre-training: avg-pool -> Linear [-> LeakyReLU -> Linear]) pools the channels_last feature map with

@@ -1,54 +1,15 @@
 // BatchNorm2d(train/eval) + ReLU (+ fused 2x2 max-pool), their backward, and the small NHWC data
-// movers (upsample backward, gradient joins, casts) plus fused Adam.
-// ref: contrastyou/arch/unet.py:16-17,19-20,34-35 (BN+ReLU), :61-64 (MaxPool2d(2,2)), :32 (Upsample x2);
-//      optimiser: semi_seg/trainer.py:67-72,179-184 (torch.optim.Adam with L2 weight decay).
+// movers (upsample backward, gradient joins, casts).  Every kernel here but bn_bwd_finalize_kernel is typed by the storage type;
+// the statistics -> coefficients kernels of the forward are in bn_coeffs.hip, fused Adam in optim.hip (no storage type: built once).
+// ref: contrastyou/arch/unet.py:16-17,19-20,34-35 (BN+ReLU), :61-64 (MaxPool2d(2,2)), :32 (Upsample x2).
 // All HBM-bound: 16-byte vectors per thread, grid-stride, deterministic two-pass channel sums.
 #include "common.h"
 
 namespace miseg {
 
-// ---- statistics -> coefficients.  saved = [mean | invstd | scale | shift] (4*C floats)
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ parts, int nparts, int C, float count,
-                                                          const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                          float momentum, float* __restrict__ rmean, float* __restrict__ rvar,
-                                                          long long* __restrict__ nbt, float* __restrict__ saved) {
-    __shared__ float red[17];
-    const int c = blockIdx.x;
-    float s1 = 0.f, s2 = 0.f;
-    for (int q = threadIdx.x; q < nparts; q += 256) {
-        s1 += parts[((size_t)q * 2 + 0) * C + c];
-        s2 += parts[((size_t)q * 2 + 1) * C + c];
-    }
-    s1 = block_sum(s1, red);
-    s2 = block_sum(s2, red);
-    if (threadIdx.x == 0) {
-        const float mean = s1 / count;
-        float var = s2 / count - mean * mean;  // biased batch variance
-        var = fmaxf(var, 0.f);
-        const float invstd = rsqrtf(var + eps);
-        const float sc = gamma[c] * invstd;
-        saved[c] = mean; saved[C + c] = invstd; saved[2 * C + c] = sc; saved[3 * C + c] = beta[c] - mean * sc;
-        if (rmean) {
-            const float unb = count > 1.f ? var * count / (count - 1.f) : var;
-            rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-            rvar[c] = (1.f - momentum) * rvar[c] + momentum * unb;
-            if (c == 0 && nbt) nbt[0] += 1;
-        }
-    }
-}
-
-__global__ void bn_eval_coeffs_kernel(int C, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                      const float* __restrict__ rmean, const float* __restrict__ rvar, float* __restrict__ saved) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < C) {
-        const float invstd = rsqrtf(rvar[c] + eps), sc = gamma[c] * invstd;
-        saved[c] = rmean[c]; saved[C + c] = invstd; saved[2 * C + c] = sc; saved[3 * C + c] = beta[c] - rmean[c] * sc;
-    }
-}
-
 // ---- ACC forms of the apply kernels: the batch statistics arrive as the two fixed-point totals per channel the producing convolution
 // accumulated (common.h bn_acc_add); every block works the coefficients out itself (C <= 256 threads, a few double operations each)
-// and keeps them in LDS, block 0 also writes `saved` for the backward and moves the running statistics -- bn_finalize_kernel's
+// and keeps them in LDS, block 0 also writes `saved` for the backward and moves the running statistics -- bn_finalize_kernel's (bn_coeffs.hip)
 // formulas with the variance taken in double.
 struct BnAccArgs {
     const unsigned long long* acc;
@@ -486,30 +447,6 @@ __global__ __launch_bounds__(256) void cast_pad_c1_kernel(const float* __restric
     }
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, int64_t n, float b1, float b2, const float* __restrict__ hyper,
-                                                   float inv_scale, const float* __restrict__ guard, int nguard) {
-    // guard: the iteration's deferred-check flags (non-zero or NaN = a check failed).  A failed check leaves parameters and moments
-    // untouched, so the exception the host raises one iteration later finds the state the reference -- which raises before
-    // backward (iic_loss.py:147-148) -- would have left.
-    for (int i = 0; i < nguard; ++i)
-        if (!(guard[i] == 0.f)) return;
-    const float step_size = hyper[0], inv_sqrt_bc2 = hyper[1], eps = hyper[2], wd = hyper[3];
-    if (inv_scale < 0.f) inv_scale = hyper[4];       // the loss scale lives on the device (dynamic scale under a replayed launch tape)
-    for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float gi = g[i] * inv_scale + wd * p[i];
-        float mi = m[i] * b1 + (1.f - b1) * gi;
-        float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        p[i] = p[i] - step_size * (mi / denom);
-    }
-}
-
-static inline int ew_blocks(int64_t n) {
-    static const int64_t cap = [] { const char* e = getenv("MISEG_EW_BLOCKS"); return e ? atoll(e) : 8192LL; }();      // grid-stride elementwise kernels
-    return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), cap));
-}
 static inline int red_blocks(int64_t npix, int CV) {
     (void)CV;
     static const int cap = [] { const char* e = getenv("MISEG_RED_BLOCKS"); return e ? atoi(e) : 512; }();
@@ -519,25 +456,6 @@ static inline int red_blocks(int64_t npix, int CV) {
 }  // namespace miseg
 
 using namespace miseg;
-
-extern "C" int miseg_bn_finalize(void* stream, const float* parts, int64_t nparts, int64_t C, int64_t count, const float* gamma,
-                                 const float* beta, float eps, float momentum, float* rmean, float* rvar, int64_t* nbt, float* saved) {
-    MISEG_TAPE(miseg_bn_finalize, stream, parts, nparts, C, count, gamma, beta, eps, momentum, rmean, rvar, nbt, saved);
-    MISEG_REQUIRE(parts && gamma && beta && saved && C > 0 && nparts > 0 && count > 0, "bn_finalize: bad args");
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)C), dim3(256), 0, as_stream(stream), parts, (int)nparts, (int)C, (float)count, gamma,
-                       beta, eps, momentum, rmean, rvar, (long long*)nbt, saved);
-    MISEG_LAUNCH_CHECK("bn_finalize_kernel");
-    return MISEG_OK;
-}
-
-extern "C" int miseg_bn_eval_coeffs(void* stream, int64_t C, const float* gamma, const float* beta, float eps, const float* rmean,
-                                    const float* rvar, float* saved) {
-    MISEG_TAPE(miseg_bn_eval_coeffs, stream, C, gamma, beta, eps, rmean, rvar, saved);
-    MISEG_REQUIRE(gamma && beta && rmean && rvar && saved && C > 0, "bn_eval_coeffs: bad args");
-    hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3((unsigned)cdiv(C, 64)), dim3(64), 0, as_stream(stream), (int)C, gamma, beta, eps, rmean, rvar, saved);
-    MISEG_LAUNCH_CHECK("bn_eval_coeffs_kernel");
-    return MISEG_OK;
-}
 
 extern "C" int miseg_bn_relu_fwd(void* stream, int dt, const void* raw, int64_t N, int64_t H, int64_t W, int64_t C, const float* saved,
                                  void* y, void* pooled) {
@@ -553,25 +471,13 @@ extern "C" int miseg_bn_relu_fwd(void* stream, int dt, const void* raw, int64_t 
     const int CV = (int)(C / V);
     if (pooled && CV <= 32 && (CV & (CV - 1)) == 0) {     // the coalesced pooled form: the partner lane L ^ CV is in the same wave
         const int nbp = ew_blocks(N * (H / 2) * W * CV);
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-        if (dt == MISEG_F32) hipLaunchKernelGGL(bn_relu_fwd_pool_kernel<float>, dim3(nbp), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)pooled);
-        else
-#endif
-        if (dt == MISEG_BF16) hipLaunchKernelGGL(bn_relu_fwd_pool_kernel<bf16>, dim3(nbp), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)pooled);
-        else return fail(MISEG_E_INVALID, "bn_relu_fwd: bad dtype");
+        MISEG_WITH_STORAGE_TYPE(dt, "bn_relu_fwd", hipLaunchKernelGGL(bn_relu_fwd_pool_kernel<TT>, dim3(nbp), dim3(256), 0, st, (const TT*)raw, (int)N, (int)H, (int)W, (int)C, saved, (TT*)y, (TT*)pooled));
         MISEG_LAUNCH_CHECK("bn_relu_fwd_pool_kernel");
         return MISEG_OK;
     }
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32) {
-        if (pooled) hipLaunchKernelGGL((bn_relu_fwd_kernel<float, true>), dim3(nb), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)pooled);
-        else hipLaunchKernelGGL((bn_relu_fwd_kernel<float, false>), dim3(nb), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)nullptr);
-    } else
-#endif
-    if (dt == MISEG_BF16) {
-        if (pooled) hipLaunchKernelGGL((bn_relu_fwd_kernel<bf16, true>), dim3(nb), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)pooled);
-        else hipLaunchKernelGGL((bn_relu_fwd_kernel<bf16, false>), dim3(nb), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)nullptr);
-    } else return fail(MISEG_E_INVALID, "bn_relu_fwd: bad dtype");
+    MISEG_WITH_STORAGE_TYPE(dt, "bn_relu_fwd",
+        if (pooled) hipLaunchKernelGGL((bn_relu_fwd_kernel<TT, true>), dim3(nb), dim3(256), 0, st, (const TT*)raw, (int)N, (int)H, (int)W, (int)C, saved, (TT*)y, (TT*)pooled);
+        else hipLaunchKernelGGL((bn_relu_fwd_kernel<TT, false>), dim3(nb), dim3(256), 0, st, (const TT*)raw, (int)N, (int)H, (int)W, (int)C, saved, (TT*)y, (TT*)nullptr));
     MISEG_LAUNCH_CHECK("bn_relu_fwd_kernel");
     return MISEG_OK;
 }
@@ -594,25 +500,13 @@ extern "C" int miseg_bn_relu_fwd_acc(void* stream, int dt, const void* raw, int6
     const int CV = (int)(C / V);
     if (pooled && CV <= 32 && (CV & (CV - 1)) == 0) {
         const int nbp = ew_blocks(N * (H / 2) * W * CV);
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-        if (dt == MISEG_F32) hipLaunchKernelGGL((bn_relu_fwd_pool_kernel<float, true>), dim3(nbp), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)pooled, a);
-        else
-#endif
-        if (dt == MISEG_BF16) hipLaunchKernelGGL((bn_relu_fwd_pool_kernel<bf16, true>), dim3(nbp), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)pooled, a);
-        else return fail(MISEG_E_INVALID, "bn_relu_fwd_acc: bad dtype");
+        MISEG_WITH_STORAGE_TYPE(dt, "bn_relu_fwd_acc", hipLaunchKernelGGL((bn_relu_fwd_pool_kernel<TT, true>), dim3(nbp), dim3(256), 0, st, (const TT*)raw, (int)N, (int)H, (int)W, (int)C, saved, (TT*)y, (TT*)pooled, a));
         MISEG_LAUNCH_CHECK("bn_relu_fwd_pool_kernel");
         return MISEG_OK;
     }
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32) {
-        if (pooled) hipLaunchKernelGGL((bn_relu_fwd_kernel<float, true, true>), dim3(nb), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)pooled, a);
-        else hipLaunchKernelGGL((bn_relu_fwd_kernel<float, false, true>), dim3(nb), dim3(256), 0, st, (const float*)raw, (int)N, (int)H, (int)W, (int)C, saved, (float*)y, (float*)nullptr, a);
-    } else
-#endif
-    if (dt == MISEG_BF16) {
-        if (pooled) hipLaunchKernelGGL((bn_relu_fwd_kernel<bf16, true, true>), dim3(nb), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)pooled, a);
-        else hipLaunchKernelGGL((bn_relu_fwd_kernel<bf16, false, true>), dim3(nb), dim3(256), 0, st, (const bf16*)raw, (int)N, (int)H, (int)W, (int)C, saved, (bf16*)y, (bf16*)nullptr, a);
-    } else return fail(MISEG_E_INVALID, "bn_relu_fwd_acc: bad dtype");
+    MISEG_WITH_STORAGE_TYPE(dt, "bn_relu_fwd_acc",
+        if (pooled) hipLaunchKernelGGL((bn_relu_fwd_kernel<TT, true, true>), dim3(nb), dim3(256), 0, st, (const TT*)raw, (int)N, (int)H, (int)W, (int)C, saved, (TT*)y, (TT*)pooled, a);
+        else hipLaunchKernelGGL((bn_relu_fwd_kernel<TT, false, true>), dim3(nb), dim3(256), 0, st, (const TT*)raw, (int)N, (int)H, (int)W, (int)C, saved, (TT*)y, (TT*)nullptr, a));
     MISEG_LAUNCH_CHECK("bn_relu_fwd_kernel");
     return MISEG_OK;
 }
@@ -649,12 +543,7 @@ static int bn_relu_bwd_impl(void* stream, int dt, const void* raw, const void* g
     MISEG_REQUIRE(!acc || nb <= kBnAccMaxBlocks, "bn_relu_bwd_acc: %d reduce blocks exceed the accumulator's no-wrap bound", nb);
     const int64_t p2lo = n2_begin * H * W, p2hi = n2_end * H * W;
 #define RED(TT, POOL) hipLaunchKernelGGL((bn_relu_bwd_reduce_kernel<TT, POOL>), dim3(nb), dim3(256), lb, st, (const TT*)raw, (const TT*)gy, (const TT*)gpool, (int)N, (int)H, (int)W, (int)C, saved, parts, fin, BnGy2<TT>{(const TT*)gy2, p2lo, p2hi})
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32) { if (gpool) RED(float, true); else RED(float, false); }
-    else
-#endif
-    if (dt == MISEG_BF16) { if (gpool) RED(bf16, true); else RED(bf16, false); }
-    else return fail(MISEG_E_INVALID, "bn_relu_bwd: bad dtype");
+    MISEG_WITH_STORAGE_TYPE(dt, "bn_relu_bwd", if (gpool) RED(TT, true); else RED(TT, false));
 #undef RED
     MISEG_LAUNCH_CHECK("bn_relu_bwd_reduce_kernel");
     if (!finish && !acc) {
@@ -666,19 +555,9 @@ static int bn_relu_bwd_impl(void* stream, int dt, const void* raw, const void* g
     const int na = ew_blocks((gpool ? npix / 4 : npix) * CV);
     const BnBwdAccArgs ba{static_cast<const unsigned long long*>(acc), gamma, ggamma, gbeta, (float)npix, training};
 #define APP(TT, POOL, ACCV) hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, POOL, ACCV>), dim3(na), dim3(256), 0, st, (const TT*)raw, (const TT*)gy, (const TT*)gpool, (int)N, (int)H, (int)W, (int)C, saved, coeffs, (TT*)graw, BnGy2<TT>{(const TT*)gy2, p2lo, p2hi}, ba)
-    if (acc) {
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-        if (dt == MISEG_F32) { if (gpool) APP(float, true, true); else APP(float, false, true); }
-        else
-#endif
-        { if (gpool) APP(bf16, true, true); else APP(bf16, false, true); }
-    } else {
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-        if (dt == MISEG_F32) { if (gpool) APP(float, true, false); else APP(float, false, false); }
-        else
-#endif
-        { if (gpool) APP(bf16, true, false); else APP(bf16, false, false); }
-    }
+    MISEG_WITH_STORAGE_TYPE(dt, "bn_relu_bwd",
+        if (acc) { if (gpool) APP(TT, true, true); else APP(TT, false, true); }
+        else { if (gpool) APP(TT, true, false); else APP(TT, false, false); });
 #undef APP
     MISEG_LAUNCH_CHECK("bn_bwd_apply_kernel");
     return MISEG_OK;
@@ -735,6 +614,7 @@ extern "C" int miseg_bn_relu_bwd_ext(void* stream, int dt, const void* raw, cons
     const int V = dt == MISEG_BF16 ? 8 : 4;
     const int CV = (int)(C / V);
     MISEG_REQUIRE(dt != MISEG_F16 && C % V == 0 && 256 % CV == 0, "bn_relu_bwd_ext: C/%d must divide 256", V);
+    MISEG_REQUIRE(storage_type_served(dt), "bn_relu_bwd_ext: bad dtype");      // before the finalize launch, which takes no type
     hipStream_t st = as_stream(stream);
     const int64_t npix = N * H * W;
     float* coeffs = (float*)ws;
@@ -742,14 +622,9 @@ extern "C" int miseg_bn_relu_bwd_ext(void* stream, int dt, const void* raw, cons
                        coeffs, ggamma, gbeta, (float*)nullptr);
     MISEG_LAUNCH_CHECK("bn_bwd_finalize_kernel");
     const int na = ew_blocks(npix * CV);
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32)
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false>), dim3(na), dim3(256), 0, st, (const float*)raw, (const float*)gy, (const float*)nullptr, (int)N,
-                           (int)H, (int)W, (int)C, saved, coeffs, (float*)graw, BnGy2<float>{nullptr, 0, 0});
-    else
-#endif
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16, false>), dim3(na), dim3(256), 0, st, (const bf16*)raw, (const bf16*)gy, (const bf16*)nullptr, (int)N,
-                           (int)H, (int)W, (int)C, saved, coeffs, (bf16*)graw, BnGy2<bf16>{nullptr, 0, 0});
+    MISEG_WITH_STORAGE_TYPE(dt, "bn_relu_bwd_ext",
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, false>), dim3(na), dim3(256), 0, st, (const TT*)raw, (const TT*)gy, (const TT*)nullptr, (int)N,
+                           (int)H, (int)W, (int)C, saved, coeffs, (TT*)graw, BnGy2<TT>{nullptr, 0, 0}));
     MISEG_LAUNCH_CHECK("bn_bwd_apply_kernel");
     return MISEG_OK;
 }
@@ -761,6 +636,7 @@ extern "C" int miseg_bn_relu_bwd_stats(void* stream, int dt, const void* raw, co
     MISEG_F16_DISPATCH_ON(dt, miseg_bn_relu_bwd_stats, stream, MISEG_BF16, raw, gy, N, H, W, C, gamma, saved, training, bwd_coef, ggamma, gbeta, ext_parts,
                           ext_nparts, ws, ws_bytes);
     MISEG_REQUIRE(bwd_coef, "bn_relu_bwd_stats: null pointer");
+    MISEG_REQUIRE(storage_type_served(dt), "bn_relu_bwd_stats: bad dtype");
     if (ext_parts) {      // the sums were taken by the epilogue of the convolution that wrote gy (miseg_conv3x3_dgrad_bn)
         MISEG_REQUIRE(gamma && saved && ggamma && gbeta && ext_nparts > 0 && C > 0, "bn_relu_bwd_stats: bad args");
         hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)C), dim3(256), 0, as_stream(stream), ext_parts, (int)ext_nparts, (int)C,
@@ -786,12 +662,7 @@ extern "C" int miseg_sumpool2x2(void* stream, int dt, const void* in, int64_t N,
     MISEG_REQUIRE(C % V == 0, "sumpool2x2: C must be a multiple of %d", V);
     const int64_t total = N * (H / 2) * (W / 2) * (C / V);
     hipStream_t st = as_stream(stream);
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32) hipLaunchKernelGGL(sumpool2x2_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, st, (const float*)in, (int)N, (int)H, (int)W, (int)C, (float*)out, accumulate);
-    else
-#endif
-    if (dt == MISEG_BF16) hipLaunchKernelGGL(sumpool2x2_kernel<bf16>, dim3(ew_blocks(total)), dim3(256), 0, st, (const bf16*)in, (int)N, (int)H, (int)W, (int)C, (bf16*)out, accumulate);
-    else return fail(MISEG_E_INVALID, "sumpool2x2: bad dtype");
+    MISEG_WITH_STORAGE_TYPE(dt, "sumpool2x2", hipLaunchKernelGGL(sumpool2x2_kernel<TT>, dim3(ew_blocks(total)), dim3(256), 0, st, (const TT*)in, (int)N, (int)H, (int)W, (int)C, (TT*)out, accumulate));
     MISEG_LAUNCH_CHECK("sumpool2x2_kernel");
     return MISEG_OK;
 }
@@ -803,12 +674,7 @@ extern "C" int miseg_axpy(void* stream, int dt, const void* src, void* dst, int6
     const int V = dt == MISEG_BF16 ? 8 : 4;
     MISEG_REQUIRE(numel % V == 0, "axpy: numel must be a multiple of %d", V);
     hipStream_t st = as_stream(stream);
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32) hipLaunchKernelGGL(axpy_kernel<float>, dim3(ew_blocks(numel / V)), dim3(256), 0, st, (const float*)src, (float*)dst, numel / V);
-    else
-#endif
-    if (dt == MISEG_BF16) hipLaunchKernelGGL(axpy_kernel<bf16>, dim3(ew_blocks(numel / V)), dim3(256), 0, st, (const bf16*)src, (bf16*)dst, numel / V);
-    else return fail(MISEG_E_INVALID, "axpy: bad dtype");
+    MISEG_WITH_STORAGE_TYPE(dt, "axpy", hipLaunchKernelGGL(axpy_kernel<TT>, dim3(ew_blocks(numel / V)), dim3(256), 0, st, (const TT*)src, (TT*)dst, numel / V));
     MISEG_LAUNCH_CHECK("axpy_kernel");
     return MISEG_OK;
 }
@@ -819,54 +685,11 @@ extern "C" int miseg_cast_pad(void* stream, const float* in, int64_t npix, int64
     MISEG_REQUIRE(in && out && Cin > 0 && CP >= Cin, "cast_pad: bad args");
     hipStream_t st = as_stream(stream);
     const int nb = ew_blocks(npix * CP);
-#ifndef MISEG_F16_BUILD      // dt_out == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt_out == MISEG_F32) hipLaunchKernelGGL((cast_pad_kernel<float, float>), dim3(nb), dim3(256), 0, st, in, (float*)out, npix, (int)Cin, (int)CP);
-    else
-#endif
-    if (dt_out == MISEG_BF16 && Cin == 1 && CP == 8) hipLaunchKernelGGL(cast_pad_c1_kernel<bf16>, dim3(ew_blocks(npix)), dim3(256), 0, st, in, (bf16*)out, npix);
-    else if (dt_out == MISEG_BF16) hipLaunchKernelGGL((cast_pad_kernel<float, bf16>), dim3(nb), dim3(256), 0, st, in, (bf16*)out, npix, (int)Cin, (int)CP);
-    else return fail(MISEG_E_INVALID, "cast_pad: bad dtype");
+    MISEG_WITH_STORAGE_TYPE(dt_out, "cast_pad",
+        if constexpr (sizeof(TT) == 2) {
+            if (Cin == 1 && CP == 8) { hipLaunchKernelGGL(cast_pad_c1_kernel<TT>, dim3(ew_blocks(npix)), dim3(256), 0, st, in, (TT*)out, npix); return; }
+        }
+        hipLaunchKernelGGL((cast_pad_kernel<float, TT>), dim3(nb), dim3(256), 0, st, in, (TT*)out, npix, (int)Cin, (int)CP));
     MISEG_LAUNCH_CHECK("cast_pad_kernel");
     return MISEG_OK;
-}
-
-extern "C" int miseg_adam_step_guarded(void* stream, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
-                                       float beta1, float beta2, const float* hyper, float grad_scale, const float* guard, int64_t nguard) {
-    MISEG_TAPE(miseg_adam_step_guarded, stream, param, grad, exp_avg, exp_avg_sq, numel, beta1, beta2, hyper, grad_scale, guard, nguard);
-    MISEG_REQUIRE(param && grad && exp_avg && exp_avg_sq && hyper && numel > 0, "adam_step: bad args");
-    MISEG_REQUIRE((grad_scale > 0.f || grad_scale == -1.f) && std::isfinite(grad_scale), "adam_step: grad_scale must be a positive finite number (or -1: read 1 / scale from hyper[4])");
-    MISEG_REQUIRE(nguard >= 0 && nguard <= 1024 && (nguard == 0 || guard), "adam_step: bad guard");
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(numel)), dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq, numel, beta1, beta2,
-                       hyper, grad_scale > 0.f ? 1.f / grad_scale : -1.f, guard, (int)nguard);
-    MISEG_LAUNCH_CHECK("adam_kernel");
-    return MISEG_OK;
-}
-namespace miseg {
-__global__ __launch_bounds__(256) void count_nonfinite_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ count) {
-    int bad = 0;
-    for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) bad += !(fabsf(g[i]) <= 3.4028234e38f);   // inf or NaN
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
-    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(count, (float)bad);       // integers below 2^24: exact in any order
-}
-}  // namespace miseg
-
-extern "C" int miseg_count_nonfinite(void* stream, const float* grad, int64_t numel, float* count) {
-    MISEG_TAPE(miseg_count_nonfinite, stream, grad, numel, count);
-    MISEG_REQUIRE(grad && count && numel > 0, "count_nonfinite: bad args");
-    hipMemsetAsync(count, 0, sizeof(float), as_stream(stream));
-    hipLaunchKernelGGL(count_nonfinite_kernel, dim3((unsigned)std::min<int64_t>(cdiv(numel, 1024), 1024)), dim3(256), 0, as_stream(stream), grad, numel, count);
-    MISEG_LAUNCH_CHECK("count_nonfinite_kernel");
-    return MISEG_OK;
-}
-
-extern "C" int miseg_adam_step_scaled(void* stream, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
-                                      float beta1, float beta2, const float* hyper, float grad_scale) {
-    MISEG_TAPE(miseg_adam_step_scaled, stream, param, grad, exp_avg, exp_avg_sq, numel, beta1, beta2, hyper, grad_scale);
-    return miseg_adam_step_guarded(stream, param, grad, exp_avg, exp_avg_sq, numel, beta1, beta2, hyper, grad_scale, nullptr, 0);
-}
-extern "C" int miseg_adam_step(void* stream, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
-                               float beta1, float beta2, const float* hyper) {
-    MISEG_TAPE(miseg_adam_step, stream, param, grad, exp_avg, exp_avg_sq, numel, beta1, beta2, hyper);
-    return miseg_adam_step_scaled(stream, param, grad, exp_avg, exp_avg_sq, numel, beta1, beta2, hyper, 1.f);
 }

@@ -7,9 +7,11 @@
 #include <string.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <type_traits>
 
 // ---- the fp16 build -------------------------------------------------------------------------------------------------------
-// bn / conv_* / heads_* / heads_var / mi_global / contrast* are compiled TWICE: as written (16-bit storage type = bf16) and with
+// The units that a storage-typed call can reach (the Makefile's TWICE: bn, conv_*, heads_* bar heads_f32, contrast,
+// contrast_decoder) are compiled TWICE: as written (16-bit storage type = bf16) and with
 // -DMISEG_F16_BUILD, where the same sources get IEEE half as their 16-bit type: `bf16` below becomes __half, the conversion helpers
 // and the MFMA builtins switch to their f16 forms, the namespace becomes miseg_f16 and every C entry point is renamed f16_miseg_*
 // (f16_rename.h, generated from the header by the Makefile).  The primary entry points forward dt == MISEG_F16 calls to those
@@ -60,16 +62,46 @@ using miseg_core::last_error_buf;
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline int ew_blocks(int64_t n) {      // grid of the grid-stride elementwise kernels (bn.hip, optim.hip)
+    static const int64_t cap = [] { const char* e = getenv("MISEG_EW_BLOCKS"); return e ? atoll(e) : 8192LL; }();
+    return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), cap));
+}
 
 // ---- element types ------------------------------------------------------------------------
 #ifdef MISEG_F16_BUILD
 typedef __half bf16;            // the 16-bit storage / operand type of this build (the name stays: the sources are shared)
+constexpr bool kServesFloat = false;
 #else
 typedef __hip_bfloat16 bf16;
+constexpr bool kServesFloat = true;
 #endif
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+// ---- run-time storage type `dt` -> compile-time element type: the one place that says which types a build serves.
+// The bf16 build serves float and bf16.  The fp16 build is entered through MISEG_F16_DISPATCH_ON alone, which re-labels
+// dt == MISEG_F16 as MISEG_BF16 (the name that build gives __half): it serves `bf16` only (kServesFloat above) and never
+// instantiates a float kernel.  f is a generic lambda called with a value of the element type; it returns nothing or a status
+// code.  Any other dt: MISEG_E_INVALID "<who>: bad dtype".
+template <typename TT, typename F> static inline int call_with_type(F&& f) {
+    if constexpr (std::is_void_v<decltype(f(TT{}))>) { f(TT{}); return MISEG_OK; }
+    else return f(TT{});
+}
+static inline bool storage_type_served(int dt) { return dt == MISEG_BF16 || (kServesFloat && dt == MISEG_F32); }
+template <typename F> static inline int with_storage_type(int dt, const char* who, F&& f) {
+    if (dt == MISEG_BF16) return call_with_type<bf16>(f);
+    if constexpr (kServesFloat) {
+        if (dt == MISEG_F32) return call_with_type<float>(f);
+    }
+    return fail(MISEG_E_INVALID, "%s: bad dtype", who);
+}
+// ... as a statement of an entry point: the body sees the element type as TT; a failure (unknown dt, or the body's own) returns.
+#define MISEG_WITH_STORAGE_TYPE(dt, who, ...)                                                                                   \
+    do {                                                                                                                        \
+        const int rc_ = ::miseg::with_storage_type(dt, who, [&](auto tt_) { using TT = decltype(tt_); __VA_ARGS__; });           \
+        if (rc_ != MISEG_OK) return rc_;                                                                                        \
+    } while (0)
 
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(bf16 v) { return __bfloat162float(v); }

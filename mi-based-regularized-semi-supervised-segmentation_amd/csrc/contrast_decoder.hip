@@ -262,17 +262,12 @@ static inline int cd_vec(int dt, int64_t C) { return dt == MISEG_F32 ? 4 : (C % 
 
 using namespace miseg;
 
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-#define CD_DISPATCH_F32(dt, LAUNCH) if (dt == MISEG_F32) { LAUNCH(float, 4); } else
-#else
-#define CD_DISPATCH_F32(dt, LAUNCH)
-#endif
-#define CD_DISPATCH(dt, C, LAUNCH)                                  \
-    do {                                                            \
-        CD_DISPATCH_F32(dt, LAUNCH)                                 \
-        if (C % 8 == 0) { LAUNCH(bf16, 8); }                        \
-        else { LAUNCH(bf16, 4); }                                   \
-    } while (0)
+// LAUNCH(type, elements per vector): float in 16-byte vectors, a 16-bit type in 16-byte vectors where C allows (cd_vec)
+#define CD_DISPATCH(dt, who, C, LAUNCH)                                      \
+    MISEG_WITH_STORAGE_TYPE(dt, who,                                         \
+        if constexpr (sizeof(TT) == 4) { LAUNCH(TT, 4); }                    \
+        else if (C % 8 == 0) { LAUNCH(TT, 8); }                              \
+        else { LAUNCH(TT, 4); })
 
 #define CD_SHAPE_CHECKS(what)                                                                                                           \
     MISEG_REQUIRE(dt == MISEG_F32 || dt == MISEG_BF16, what ": unknown dt");                                                           \
@@ -291,7 +286,7 @@ extern "C" int miseg_bias_lrelu_fwd(void* stream, int dt, const void* raw, int64
     const unsigned grid = (unsigned)std::min<int64_t>(cdiv((int64_t)nvec, 256), kCdMaxBlocks);
     hipStream_t st = as_stream(stream);
 #define L(TT, VV) hipLaunchKernelGGL((bias_lrelu_fwd_kernel<TT, VV>), dim3(grid), dim3(256), 0, st, (const TT*)raw, nvec, cvn, bias, slope, (TT*)y)
-    CD_DISPATCH(dt, C, L);
+    CD_DISPATCH(dt, "bias_lrelu_fwd", C, L);
 #undef L
     MISEG_LAUNCH_CHECK("bias_lrelu_fwd_kernel");
     return MISEG_OK;
@@ -319,7 +314,7 @@ extern "C" int miseg_bias_lrelu_bwd(void* stream, int dt, const void* y, const v
     float* parts = (float*)ws;
     const size_t lds = (size_t)rpb * C * 4;
 #define L(TT, VV) hipLaunchKernelGGL((bias_lrelu_bwd_kernel<TT, VV>), dim3(nblocks), dim3(256), lds, st, (const TT*)y, (const TT*)gy, npix, cvn, slope, (TT*)gx, parts)
-    CD_DISPATCH(dt, C, L);
+    CD_DISPATCH(dt, "bias_lrelu_bwd", C, L);
 #undef L
     MISEG_LAUNCH_CHECK("bias_lrelu_bwd_kernel");
     hipLaunchKernelGGL(bias_parts_reduce_kernel, dim3(reduce_grid(C, nblocks)), dim3(256), 0, st, (const float*)parts, nblocks, (int)C, gbias);
@@ -348,7 +343,7 @@ extern "C" int miseg_bias_amaxpool_fwd(void* stream, int dt, const void* raw, in
     const unsigned grid = (unsigned)(N * OH * OW);
     hipStream_t st = as_stream(stream);
 #define L(TT, VV) hipLaunchKernelGGL((bias_amaxpool_fwd_kernel<TT, VV>), dim3(grid), dim3(256), lds, st, (const TT*)raw, g, bias, e, idx)
-    CD_DISPATCH(dt, C, L);
+    CD_DISPATCH(dt, "bias_amaxpool_fwd", C, L);
 #undef L
     MISEG_LAUNCH_CHECK("bias_amaxpool_fwd_kernel");
     return MISEG_OK;
@@ -367,7 +362,7 @@ extern "C" int miseg_bias_amaxpool_bwd(void* stream, int dt, const float* ge, co
     const unsigned grid = (unsigned)std::min<int64_t>(cdiv((int64_t)nvec, 256), 4 * kCdMaxBlocks);
     hipStream_t st = as_stream(stream);
 #define L(TT, VV) hipLaunchKernelGGL((bias_amaxpool_bwd_kernel<TT, VV>), dim3(grid), dim3(256), 0, st, ge, idx, g, nvec, (TT*)graw)
-    CD_DISPATCH(dt, C, L);
+    CD_DISPATCH(dt, "bias_amaxpool_bwd", C, L);
 #undef L
     MISEG_LAUNCH_CHECK("bias_amaxpool_bwd_kernel");
     if (gbias) {

@@ -316,14 +316,8 @@ extern "C" int miseg_pack_conv3x3_weights(void* stream, int dt, const float* w, 
     MISEG_REQUIRE(ci_begin >= 0 && ci_count > 0 && ci_begin + ci_count <= Cin, "pack_conv3x3_weights: bad channel slice");
     const int total = (int)(9 * ((kind & 0xff) ? ci_count * Cout : Cout * Cin));
     const int nb = std::min((total + 255) / 256, 1024);
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32)
-        hipLaunchKernelGGL(pack_w_kernel<float>, dim3(nb), dim3(256), 0, as_stream(stream), w, (int)Cout, (int)Cin, kind, (int)ci_begin, (int)ci_count, (float*)packed);
-    else
-#endif
-    if (dt == MISEG_BF16)
-        hipLaunchKernelGGL(pack_w_kernel<bf16>, dim3(nb), dim3(256), 0, as_stream(stream), w, (int)Cout, (int)Cin, kind, (int)ci_begin, (int)ci_count, (bf16*)packed);
-    else return fail(MISEG_E_INVALID, "pack_conv3x3_weights: bad dtype");
+    MISEG_WITH_STORAGE_TYPE(dt, "pack_conv3x3_weights",
+        hipLaunchKernelGGL(pack_w_kernel<TT>, dim3(nb), dim3(256), 0, as_stream(stream), w, (int)Cout, (int)Cin, kind, (int)ci_begin, (int)ci_count, (TT*)packed));
     MISEG_LAUNCH_CHECK("pack_w_kernel");
     return MISEG_OK;
 }
@@ -333,14 +327,8 @@ extern "C" int miseg_pack_conv3x3_weights_multi(void* stream, int dt, const void
     MISEG_F16_DISPATCH_ON(dt, miseg_pack_conv3x3_weights_multi, stream, MISEG_BF16, jobs_dev, njobs, total_blocks);
     MISEG_REQUIRE(jobs_dev && njobs > 0 && total_blocks > 0, "pack_conv3x3_weights_multi: bad args");
     static_assert(sizeof(PackJob) == 40, "PackJob layout must match miseg_pack_job");
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32)
-        hipLaunchKernelGGL(pack_w_multi_kernel<float>, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream), (const PackJob*)jobs_dev, (int)njobs);
-    else
-#endif
-    if (dt == MISEG_BF16)
-        hipLaunchKernelGGL(pack_w_multi_kernel<bf16>, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream), (const PackJob*)jobs_dev, (int)njobs);
-    else return fail(MISEG_E_INVALID, "pack_conv3x3_weights_multi: bad dtype");
+    MISEG_WITH_STORAGE_TYPE(dt, "pack_conv3x3_weights_multi",
+        hipLaunchKernelGGL(pack_w_multi_kernel<TT>, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream), (const PackJob*)jobs_dev, (int)njobs));
     MISEG_LAUNCH_CHECK("pack_w_multi_kernel");
     return MISEG_OK;
 }
@@ -403,21 +391,15 @@ extern "C" int miseg_conv1x1_fwd(void* stream, int dt, const void* in, int64_t N
     const int64_t npix = N * H * W;
     const int nb = (int)std::min<int64_t>(cdiv(npix, 256), 4096);
     hipStream_t st = as_stream(stream);
-#define L16(CO) hipLaunchKernelGGL((conv1x1_fwd_kernel<bf16, 16, CO>), dim3(nb), dim3(256), 0, st, (const bf16*)in, npix, w, bias, out)
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-#define L(CO)                                                                                                                      \
-    if (dt == MISEG_F32) hipLaunchKernelGGL((conv1x1_fwd_kernel<float, 16, CO>), dim3(nb), dim3(256), 0, st, (const float*)in, npix, w, bias, out); \
-    else L16(CO)
-#else
-#define L(CO) L16(CO)
-#endif
-    switch (Cout) {
-        case 1: L(1); break; case 2: L(2); break; case 3: L(3); break; case 4: L(4); break;
-        case 5: L(5); break; case 8: L(8); break;
-        default: return fail(MISEG_E_INVALID, "conv1x1_fwd: unsupported Cout %ld", (long)Cout);
-    }
+#define L(CO) hipLaunchKernelGGL((conv1x1_fwd_kernel<TT, 16, CO>), dim3(nb), dim3(256), 0, st, (const TT*)in, npix, w, bias, out)
+    MISEG_WITH_STORAGE_TYPE(dt, "conv1x1_fwd",
+        switch (Cout) {
+            case 1: L(1); break; case 2: L(2); break; case 3: L(3); break; case 4: L(4); break;
+            case 5: L(5); break; case 8: L(8); break;
+            default: return fail(MISEG_E_INVALID, "conv1x1_fwd: unsupported Cout %ld", (long)Cout);
+        }
+        return MISEG_OK);
 #undef L
-#undef L16
     MISEG_LAUNCH_CHECK("conv1x1_fwd_kernel");
     return MISEG_OK;
 }
@@ -438,21 +420,15 @@ extern "C" int miseg_conv1x1_bwd(void* stream, int dt, const void* in, const flo
     const int64_t npix = N * H * W;
     const int nb = c1_blocks(npix);
     hipStream_t st = as_stream(stream);
-#define L16(CO) hipLaunchKernelGGL((conv1x1_bwd_kernel<bf16, 16, CO>), dim3(nb), dim3(256), 0, st, (const bf16*)in, gout, npix, w, (bf16*)gin, (float*)ws)
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-#define L(CO)                                                                                                                                  \
-    if (dt == MISEG_F32) hipLaunchKernelGGL((conv1x1_bwd_kernel<float, 16, CO>), dim3(nb), dim3(256), 0, st, (const float*)in, gout, npix, w, (float*)gin, (float*)ws); \
-    else L16(CO)
-#else
-#define L(CO) L16(CO)
-#endif
-    switch (Cout) {
-        case 1: L(1); break; case 2: L(2); break; case 3: L(3); break; case 4: L(4); break;
-        case 5: L(5); break; case 8: L(8); break;
-        default: return fail(MISEG_E_INVALID, "conv1x1_bwd: unsupported Cout %ld", (long)Cout);
-    }
+#define L(CO) hipLaunchKernelGGL((conv1x1_bwd_kernel<TT, 16, CO>), dim3(nb), dim3(256), 0, st, (const TT*)in, gout, npix, w, (TT*)gin, (float*)ws)
+    MISEG_WITH_STORAGE_TYPE(dt, "conv1x1_bwd",
+        switch (Cout) {
+            case 1: L(1); break; case 2: L(2); break; case 3: L(3); break; case 4: L(4); break;
+            case 5: L(5); break; case 8: L(8); break;
+            default: return fail(MISEG_E_INVALID, "conv1x1_bwd: unsupported Cout %ld", (long)Cout);
+        }
+        return MISEG_OK);
 #undef L
-#undef L16
     MISEG_LAUNCH_CHECK("conv1x1_bwd_kernel");
     const int len = (int)(Cout * Cin + Cout);
     // the blocks' [gw | gbias] partial vectors, summed straight into the two gradients

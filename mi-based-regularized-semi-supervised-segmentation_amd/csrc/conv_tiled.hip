@@ -291,12 +291,13 @@ static int launch_tiled(dim3 grid, hipStream_t st, const ConvSrc& s, int N, int 
 
 int launch_conv_tiled(int dt, int cot, int tw, int th, bool pool, dim3 grid, hipStream_t st, const ConvSrc& s, int N, int H, int W, const void* wpk,
                       int Cout, void* out, float* stats, const BnFinish& fin, const BnLoad& bl, const BnRed& br) {
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h), which therefore has no conv_tiled_f32 unit
-    if (dt == MISEG_F32) return launch_conv_tiled_f32(cot, tw, th, pool, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br);
-#endif
-    if (bl.gy || br.raw) return launch_conv_tiled_bn(cot, tw, th, pool, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br);
+    // the float kernels are in conv_tiled_f32.hip, a unit the fp16 build does not have
     // not built (tiled_shape_built): 64-channel slices of 8-row tiles, not pooled -- tiled_shape gives an 8-row tile 32
-    MISEG_TILED_SELECT_16BIT(launch_tiled, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br)
+    MISEG_WITH_STORAGE_TYPE(dt, "conv3x3",
+        if constexpr (std::is_same_v<TT, float>) return launch_conv_tiled_f32(cot, tw, th, pool, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br);
+        else if (bl.gy || br.raw) return launch_conv_tiled_bn(cot, tw, th, pool, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br);
+        else { MISEG_TILED_SELECT_16BIT(launch_tiled, grid, st, s, N, H, W, wpk, Cout, out, stats, fin, bl, br) });
+    return MISEG_OK;
 }
 
 }  // namespace miseg

@@ -428,14 +428,11 @@ static int head_local_bwd_impl(void* stream, int dt, const void* feat, int64_t B
                                (int)M, w, bias, (int)S, 1.0f / T, prob, gprob, (bf16*)gfeat, partials, accumulate);
     } else {
         const HeadBwdFused a{nblk, lds, st, feat, (int)H, (int)W, (int)C, src, flips, (int)M, w, (int)S, (int)K, 1.0f / T, prob, gprob, gfeat, partials, accumulate};
-        int rc;
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h), which therefore has no heads_f32 unit
-        if (dt == MISEG_F32) rc = launch_head_bwd_fused_f32(a);
-        else
-#endif
-        if (dt == MISEG_BF16) rc = launch_head_bwd_fused(a);
-        else return fail(MISEG_E_INVALID, "head_local_bwd: bad dtype %d", dt);
-        if (rc != MISEG_OK) return rc;
+        if (!storage_type_served(dt)) return fail(MISEG_E_INVALID, "head_local_bwd: bad dtype %d", dt);
+        // the float kernel is in heads_f32.hip, a unit the fp16 build does not have
+        MISEG_WITH_STORAGE_TYPE(dt, "head_local_bwd",
+            if constexpr (std::is_same_v<TT, float>) return launch_head_bwd_fused_f32(a);
+            else return launch_head_bwd_fused(a));
     }
     MISEG_LAUNCH_CHECK("head_local_bwd_fused_kernel");
     const int len = R * (int)C + R;

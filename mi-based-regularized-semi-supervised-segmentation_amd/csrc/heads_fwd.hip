@@ -144,7 +144,7 @@ extern "C" int miseg_head_local_fwd(void* stream, int dt, const void* feat, int6
     size_t ldsb = (size_t)K * kHT * 4;
     hipStream_t st = as_stream(stream);
     HeadFwd a{grid, ldsb, st, feat, (int)H, (int)W, (int)C, src, flips, (int)M, w, b, (int)S, (int)K, 1.0f / T, prob, simplex_tol, simplex_violations};
-    int rc = MISEG_OK;
+    if (!storage_type_served(dt)) return fail(MISEG_E_INVALID, "head_local_fwd: bad dtype %d", dt);
     if (dt == MISEG_BF16 && K == 20 && (C == 16 || C == 32) && (H * W) % 4 == 0 && S * K * C <= 3200) {
         const dim3 gridm((unsigned)cdiv(H * W, kHT * 4), (unsigned)M);
         if (C == 32)
@@ -153,27 +153,19 @@ extern "C" int miseg_head_local_fwd(void* stream, int dt, const void* feat, int6
         else
             hipLaunchKernelGGL(head_local_fwd_mfma_kernel<16>, gridm, dim3(kHT), head_mfma_lds<16>(S), st, (const bf16*)feat, (int)H, (int)W,
                                src, flips, (int)M, w, b, (int)S, 1.0f / T, prob, simplex_tol, simplex_violations);
-    } else
-    if (K <= 32 && (dt == MISEG_F32 || dt == MISEG_BF16)) {
+    } else if (K <= 32) {
         const bool quad = (H * W) % 4 == 0 && W % 4 == 0;
         if (quad) a.grid = dim3((unsigned)cdiv(H * W, kHT * 4), (unsigned)M);
         a.lds = (size_t)(S * K * C * 4);
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h), which therefore has no heads_f32 unit
-        if (dt == MISEG_F32) rc = launch_head_fwd_reg_f32(a, quad);
-        else
-#endif
-            rc = launch_head_fwd_reg<bf16>(a, quad);
-    } else
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32)
-        rc = launch_head_fwd_lds_f32(a);
-    else
-#endif
-    if (dt == MISEG_BF16)
-        rc = launch_head_fwd_lds<bf16>(a);
-    else
-        return fail(MISEG_E_INVALID, "head_local_fwd: bad dtype %d", dt);
-    if (rc != MISEG_OK) return rc;
+        // the float kernels are in heads_f32.hip, a unit the fp16 build does not have
+        MISEG_WITH_STORAGE_TYPE(dt, "head_local_fwd",
+            if constexpr (std::is_same_v<TT, float>) return launch_head_fwd_reg_f32(a, quad);
+            else return launch_head_fwd_reg<TT>(a, quad));
+    } else {
+        MISEG_WITH_STORAGE_TYPE(dt, "head_local_fwd",
+            if constexpr (std::is_same_v<TT, float>) return launch_head_fwd_lds_f32(a);
+            else return launch_head_fwd_lds<TT>(a));
+    }
     MISEG_LAUNCH_CHECK("head_local_fwd_kernel");
     return MISEG_OK;
 }

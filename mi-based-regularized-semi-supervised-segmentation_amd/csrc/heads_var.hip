@@ -3,7 +3,7 @@
 //   head_type = "mlp" : Linear/1x1-conv(C -> HID) -> LeakyReLU(0.01) -> Linear/1x1-conv(HID -> K)     (HID = 128 global, 64 local)
 //   normalize = true  : logits L2-normalised over the class axis (F.normalize, eps 1e-12) before softmax(. / T)
 // for both the pooled ("global", ClusterHead) and the per-pixel ("local", LocalClusterHead) head, forward and backward, with
-// the same fused sample gather / flip replay as the linear kernels of heads_*.hip / mi_global.hip.  Generic in C, HID, K (no
+// the same fused sample gather / flip replay as the linear kernels of heads_*.hip / heads_global.hip.  Generic in C, HID, K (no
 // template specialisation per shape: these are not on the bench path); fp32 arithmetic in channel order; parameter gradients
 // as deterministic per-block partials + a fixed-order reduce.  HID == 0 selects the single-layer head (w1 = [S][K][C]).
 #include "common.h"
@@ -398,17 +398,10 @@ extern "C" int miseg_head_local_var_fwd(void* stream, int dt, const void* feat, 
     MISEG_REQUIRE(lds <= 150 * 1024, "head_local_var_fwd: C + HID + K too large for LDS (%zu bytes)", lds);
     hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)cdiv(H * W, kVT), (unsigned)M);
-#define GO(TT)                                                                                                                      \
-    {                                                                                                                               \
-        hipFuncSetAttribute((const void*)head_local_var_fwd_kernel<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);       \
-        hipLaunchKernelGGL(head_local_var_fwd_kernel<TT>, grid, dim3(kVT), lds, st, (const TT*)feat, (int)H, (int)W, (int)C, src, flips, \
-                           (int)M, w1, b1, (int)HID, w2, b2, (int)S, (int)K, 1.f / T, normalize, prob);                             \
-    }
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32) GO(float) else
-#endif
-    GO(bf16)
-#undef GO
+    MISEG_WITH_STORAGE_TYPE(dt, "head_local_var_fwd",
+        hipFuncSetAttribute((const void*)head_local_var_fwd_kernel<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(head_local_var_fwd_kernel<TT>, grid, dim3(kVT), lds, st, (const TT*)feat, (int)H, (int)W, (int)C, src, flips,
+                           (int)M, w1, b1, (int)HID, w2, b2, (int)S, (int)K, 1.f / T, normalize, prob));
     MISEG_LAUNCH_CHECK("head_local_var_fwd_kernel");
     return MISEG_OK;
 }
@@ -437,17 +430,10 @@ extern "C" int miseg_head_local_var_bwd(void* stream, int dt, const void* feat, 
     float* partials = (float*)ws;
     float* reduced = partials + (size_t)nblk * stride;
     if (hipMemsetAsync(partials, 0, (size_t)nblk * stride * 4, st) != hipSuccess) return fail(MISEG_E_LAUNCH, "head_local_var_bwd: memset failed");
-#define GO(TT)                                                                                                                      \
-    {                                                                                                                               \
-        hipFuncSetAttribute((const void*)head_local_var_bwd_kernel<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);       \
-        hipLaunchKernelGGL(head_local_var_bwd_kernel<TT>, dim3((unsigned)nblk), dim3(kVT), lds, st, (const TT*)feat, (int)H, (int)W, (int)C, \
-                           src, flips, (int)M, w1, b1, (int)HID, w2, b2, (int)S, (int)K, 1.f / T, normalize, gprob, (TT*)gfeat, partials, nblk); \
-    }
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32) GO(float) else
-#endif
-    GO(bf16)
-#undef GO
+    MISEG_WITH_STORAGE_TYPE(dt, "head_local_var_bwd",
+        hipFuncSetAttribute((const void*)head_local_var_bwd_kernel<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(head_local_var_bwd_kernel<TT>, dim3((unsigned)nblk), dim3(kVT), lds, st, (const TT*)feat, (int)H, (int)W, (int)C,
+                           src, flips, (int)M, w1, b1, (int)HID, w2, b2, (int)S, (int)K, 1.f / T, normalize, gprob, (TT*)gfeat, partials, nblk));
     MISEG_LAUNCH_CHECK("head_local_var_bwd_kernel");
     hipLaunchKernelGGL(head_var_reduce_kernel, dim3((unsigned)cdiv((int64_t)stride, 256)), dim3(256), 0, st, partials, nblk, stride, (int)stride, reduced);
     hipLaunchKernelGGL(head_var_scatter_kernel, dim3((unsigned)cdiv((int64_t)stride, 256)), dim3(256), 0, st, reduced, (int)S, (int)C, (int)HID, (int)K,
@@ -466,12 +452,8 @@ extern "C" int miseg_head_global_var_fwd(void* stream, int dt, const void* feat,
     const size_t lds = local_fwd_lds(C, HID, K);
     MISEG_REQUIRE(lds <= 150 * 1024, "head_global_var_fwd: C + HID + K too large for LDS (%zu bytes)", lds);
     hipStream_t st = as_stream(stream);
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-    if (dt == MISEG_F32)
-        hipLaunchKernelGGL(head_var_pool_kernel<float>, dim3((unsigned)M, (unsigned)cdiv(C, 64)), dim3(256), 0, st, (const float*)feat, (int)(H * W), (int)C, src, pooled);
-    else
-#endif
-        hipLaunchKernelGGL(head_var_pool_kernel<bf16>, dim3((unsigned)M, (unsigned)cdiv(C, 64)), dim3(256), 0, st, (const bf16*)feat, (int)(H * W), (int)C, src, pooled);
+    MISEG_WITH_STORAGE_TYPE(dt, "head_global_var_fwd",
+        hipLaunchKernelGGL(head_var_pool_kernel<TT>, dim3((unsigned)M, (unsigned)cdiv(C, 64)), dim3(256), 0, st, (const TT*)feat, (int)(H * W), (int)C, src, pooled));
     MISEG_LAUNCH_CHECK("head_var_pool_kernel");
     hipFuncSetAttribute((const void*)head_global_var_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(head_global_var_fwd_kernel, dim3((unsigned)cdiv(M, kVT), (unsigned)S), dim3(kVT), lds, st, pooled, (int)M, (int)C, w1, b1,
@@ -497,14 +479,9 @@ extern "C" int miseg_head_global_var_bwd(void* stream, int dt, int64_t B, int64_
     MISEG_LAUNCH_CHECK("head_global_var_bwd_kernel");
     if (gfeat) {
         const unsigned chunks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(32, cdiv(H * W * C, 256 * 8)));
-#ifndef MISEG_F16_BUILD      // dt == MISEG_F32 never reaches the fp16 build (conv.h)
-        if (dt == MISEG_F32)
-            hipLaunchKernelGGL(head_global_var_feat_kernel<float>, dim3((unsigned)M, chunks), dim3(256), (size_t)C * 4, st, dpool_ws, (int)S, (int)M,
-                               (int)(H * W), (int)C, src, (float*)gfeat);
-        else
-#endif
-            hipLaunchKernelGGL(head_global_var_feat_kernel<bf16>, dim3((unsigned)M, chunks), dim3(256), (size_t)C * 4, st, dpool_ws, (int)S, (int)M,
-                               (int)(H * W), (int)C, src, (bf16*)gfeat);
+        MISEG_WITH_STORAGE_TYPE(dt, "head_global_var_bwd",
+            hipLaunchKernelGGL(head_global_var_feat_kernel<TT>, dim3((unsigned)M, chunks), dim3(256), (size_t)C * 4, st, dpool_ws, (int)S, (int)M,
+                               (int)(H * W), (int)C, src, (TT*)gfeat));
         MISEG_LAUNCH_CHECK("head_global_var_feat_kernel");
     }
     return MISEG_OK;

@@ -389,7 +389,6 @@ extern "C" int miseg_flip(void* stream, const void* in, void* out, int64_t N, in
                           const int64_t* is, const int64_t* os, int elem_bytes, const int32_t* flips) {
     // the stride arrays are HOST memory read during this call: a recorded call keeps its own copy of them
     ::miseg_core::TapeScope miseg_tape_scope_;
-#ifndef MISEG_F16_BUILD
     if (::miseg_core::tape_depth == 1 && ::miseg_core::tape_recording() && is && os) {
         auto* op = new ::miseg_core::TapeFnOp();
         struct Call { void* stream; const void* in; void* out; int64_t n, c, h, w, is[4], os[4]; int eb; const int32_t* flips; };
@@ -400,7 +399,6 @@ extern "C" int miseg_flip(void* stream, const void* in, void* out, int64_t N, in
         op->ptrs = {&call->in, const_cast<const void**>(reinterpret_cast<void**>(&call->out)), reinterpret_cast<const void**>(&call->flips)};
         ::miseg_core::tape_push(op);
     }
-#endif
     MISEG_REQUIRE(in && out && is && os && flips, "flip: null pointer");
     MISEG_REQUIRE(in != out, "flip: in-place not supported");
     const int64_t total = N * C * H * W;

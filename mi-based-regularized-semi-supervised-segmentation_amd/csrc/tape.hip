@@ -344,7 +344,7 @@ extern "C" int miseg_gather_rows(void* stream, const float* src, float* dst, int
     return MISEG_OK;
 }
 
-// grid of the 16-byte fill / copy / assemble kernels (bn.hip has ew_blocks, another rule: MISEG_EW_BLOCKS)
+// grid of the 16-byte fill / copy / assemble kernels (common.h has ew_blocks, another rule: MISEG_EW_BLOCKS)
 static inline int copy_blocks(int64_t n16) { return (int)std::max<int64_t>(1, std::min<int64_t>((n16 + 255) / 256, 2048)); }
 
 extern "C" int miseg_fill_zero(void* stream, void* dst, int64_t nbytes) {

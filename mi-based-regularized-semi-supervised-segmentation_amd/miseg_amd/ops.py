@@ -958,7 +958,7 @@ def softmax_entropy(logits: Tensor) -> Tensor:
     return _SoftmaxEntropy.apply(logits)
 
 
-_SUPCON_MAX_N, _SUPCON_MAX_D = 1024, 1024     # kSupMaxN / kSupMaxD of csrc/contrast.hip
+_SUPCON_MAX_N, _SUPCON_MAX_D = 1024, 1024     # kSupMaxN / kSupMaxD of csrc/supcon.hip
 
 
 def supcon_supported(n: int, d: int, views: int = 2) -> bool:

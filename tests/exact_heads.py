@@ -1,7 +1,7 @@
 """float64 references, dyadic input recipes and the dispatch mirror of the cluster-head tests (test_cpu_exact_heads.py,
 test_gpu_exact_heads.py, test_gpu_heads_fp64.py), in the style of exact_ref.py.
 
-The head backward kernels (csrc/heads_bwd.hip, csrc/heads_bwd_fused.h, csrc/mi_global.hip) take the probabilities and their gradient as INPUTS.  Their arithmetic is
+The head backward kernels (csrc/heads_bwd.hip, csrc/heads_bwd_fused.h, csrc/heads_global.hip) take the probabilities and their gradient as INPUTS.  Their arithmetic is
 dot = sum_k g p, dz = p (g - dot) / T, a hi + lo split of dz and of W into the 16-bit type, matrix-core sums in fp32 and one rounding
 to the storage type.  On dyadic inputs every one of these steps is exact: p = j / den on the simplex, g and the features small integers,
 W small integers (or multiples of 1/64), T a power of two.  Every product and partial sum is then a multiple of one power of two and

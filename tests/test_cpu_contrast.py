@@ -185,7 +185,7 @@ def test_supcon_supported_mirrors_the_kernels_range():
     assert ops.supcon_supported(9, 64, 3) and ops.supcon_supported(2, 64, 2)
     assert not ops.supcon_supported(8, 64, 1) and not ops.supcon_supported(9, 64, 2) and not ops.supcon_supported(0, 64, 2)
     assert not ops.supcon_supported(1026, 64, 2) and not ops.supcon_supported(8, 66, 2) and not ops.supcon_supported(8, 2048, 2)
-    src = open(os.path.join(PKG, "csrc", "contrast.hip")).read()
+    src = open(os.path.join(PKG, "csrc", "supcon.hip")).read()
     assert "kSupMaxN = 1024, kSupMaxD = 1024" in src and (ops._SUPCON_MAX_N, ops._SUPCON_MAX_D) == (1024, 1024)
 
 

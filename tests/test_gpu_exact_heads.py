@@ -1,4 +1,4 @@
-"""Bit-exact tests of the cluster-head backward kernels (csrc/heads_bwd.hip, csrc/heads_bwd_fused.h, csrc/mi_global.hip) on dyadic data.
+"""Bit-exact tests of the cluster-head backward kernels (csrc/heads_bwd.hip, csrc/heads_bwd_fused.h, csrc/heads_global.hip) on dyadic data.
 
 The backward kernels take prob and gprob as inputs: dot = sum g p, dz = p (g - dot) / T, a hi + lo 16-bit split of dz and W, fp32
 matrix-core sums, one rounding to the storage type.  On the recipes of tests/exact_heads.py (p = j / den on the simplex, integer g and
@@ -26,6 +26,7 @@ the library's own queries).  16-bit = bf16 and, through the -DMISEG_F16_BUILD tw
   test_local_head_backward_with_split_weights       wave and BF kernels with W = n / 64 (non-zero W-lo plane, dz inside the 16-bit type)
   test_local_head_backward_refusals                 C % 4 != 0, S K > 256, a workspace one byte short, R = 256 with C = 128 (LDS)
   test_global_head_pool_and_backward                head_pool_kernel, head_global_bwd_kernel, head_global_bwd_feat_kernel (+ _rows)
+  test_unknown_storage_type_is_refused_before_any_launch   dt = 7 through the entry points that used to launch their 16-bit kernels on it
 sum_partials_kernel runs behind every local case.  The forward kernels are in test_gpu_heads_fp64.py (float64 comparison: they go through exp).
 Not covered here: head_local_bwd_wave_kernel<16,true> (miseg_head_local_bwd_recompute) runs the softmax, so it is not exact by design;
 test_gpu_mi.py::test_local_head_backward_recomputing_the_probabilities_is_bit_equal ties it bit for bit to the reading form above.
@@ -243,3 +244,56 @@ def test_global_head_pool_and_backward(name, dtype):
         assert torch.equal(gw.cpu().to(F64), c["gw"]) and torch.equal(gb.cpu().to(F64), c["gb"])
         assert torch.equal(dz.cpu().to(F64), E.dz_ref(c["prob"], c["gprob"], c["T"]))
         assert torch.equal(host(gfeat), want)
+
+
+UNKNOWN_DT = 7        # none of MISEG_F32, MISEG_BF16, MISEG_F16
+
+
+def _unknown_dt_calls():
+    """Entry point -> (arguments after the stream and dt, outputs).  The entry points that used to hand an unknown storage type to their
+    16-bit kernels, each at the smallest shape its own test uses (bn_relu_bwd_ext and the ext_parts form of
+    bn_relu_bwd_stats have no direct test: one 4 x 4 map of 8 channels).  Every tensor is a device buffer sized for FLOAT storage, so
+    a 16-bit kernel launched on it by mistake stays inside it; every output is filled with the sentinel."""
+    def ones(*shape):
+        return torch.ones(shape, dtype=torch.float32, device=DEV)
+
+    def out(*shape):
+        return torch.full(shape, SENTINEL, dtype=torch.float32, device=DEV)
+
+    abi = _abi()
+    ch, h, s, k, m = E.GLOBAL_CASES[min(E.GLOBAL_CASES, key=lambda n: E.GLOBAL_CASES[n][0] * E.GLOBAL_CASES[n][1] ** 2 * E.GLOBAL_CASES[n][4])]
+    b, src = m + 1, i32(range(m, 0, -1))
+    pooled, prob, gfeat, gw, gb, dz = out(m, ch), out(s, m, k), out(b, h, h, ch), out(s, k, ch), out(s, k), out(s, m, k)
+    bwd = (b, h, h, ch, ptr(src), m, ptr(ones(s, k, ch)), s, k, 1.0, ptr(ones(m, ch)), ptr(ones(s, m, k) / k), ptr(ones(s, m, k)))
+    n, c = 1, 8
+    graw, ggamma, gbeta, coeffs, coef6 = out(n, 4, 4, c), out(c), out(c), out(3, c), out(6, c)
+    bn = (ptr(ones(n, 4, 4, c)), ptr(ones(n, 4, 4, c)), n, 4, 4, c, ptr(ones(c)), ptr(ones(4, c)), 1)
+    n1, h1, w1 = min(R.C1X1_SHAPES.values(), key=lambda t: t[0] * t[1] * t[2])
+    cout = min(R.C1X1_COUTS)
+    ws1 = out(abi.query("miseg_conv1x1_bwd_ws_bytes", n1, h1, w1, 16, cout) // 4 + 1)
+    logits, gin, gw1, gb1 = out(n1, h1, w1, cout), out(n1, h1, w1, 16), out(cout, 16), out(cout)
+    x1 = ones(n1, h1, w1, 16)
+    return {
+        "miseg_head_global_fwd": ((ptr(ones(b, h, h, ch)), b, h, h, ch, ptr(src), m, ptr(ones(s, k, ch)), ptr(ones(s, k)), s, k, 1.0, ptr(pooled), ptr(prob)),
+                                  [pooled, prob]),
+        "miseg_head_global_bwd": (bwd + (ptr(gfeat), ptr(gw), ptr(gb), ptr(dz)), [gfeat, gw, gb, dz]),
+        "miseg_head_global_bwd_rows": (bwd + (ptr(gfeat), 0, ptr(gw), ptr(gb), ptr(dz)), [gfeat, gw, gb, dz]),
+        "miseg_bn_relu_bwd_ext": (bn + (ptr(graw), ptr(ggamma), ptr(gbeta), ptr(ones(2, 2, c)), 2, ptr(coeffs), coeffs.numel() * 4), [graw, ggamma, gbeta, coeffs]),
+        "miseg_bn_relu_bwd_stats": (bn + (ptr(coef6), ptr(ggamma), ptr(gbeta), ptr(ones(2, 2, c)), 2, ptr(coeffs), coeffs.numel() * 4), [coef6, ggamma, gbeta]),
+        "miseg_conv1x1_fwd": ((ptr(x1), n1, h1, w1, 16, ptr(ones(cout, 16)), ptr(ones(cout)), cout, ptr(logits)), [logits]),
+        "miseg_conv1x1_bwd": ((ptr(x1), ptr(ones(n1, h1, w1, cout)), n1, h1, w1, 16, ptr(ones(cout, 16)), cout, ptr(gin), ptr(gw1), ptr(gb1), ptr(ws1),
+                               ws1.numel() * 4), [gin, gw1, gb1, ws1]),
+    }
+
+
+@pytest.mark.parametrize("entry", ["miseg_head_global_fwd", "miseg_head_global_bwd", "miseg_head_global_bwd_rows", "miseg_bn_relu_bwd_ext",
+                                   "miseg_bn_relu_bwd_stats", "miseg_conv1x1_fwd", "miseg_conv1x1_bwd"])
+def test_unknown_storage_type_is_refused_before_any_launch(entry):
+    """A storage type that is none of the three is MISEG_E_INVALID "bad dtype" before the entry point's first launch: no output is touched."""
+    abi = _abi()
+    args, outputs = _unknown_dt_calls()[entry]
+    with pytest.raises(abi.MisegError, match="bad dtype"):
+        abi.call(entry, st(), UNKNOWN_DT, *args)
+    torch.cuda.synchronize()
+    for t in outputs:
+        assert bool((t == SENTINEL).all()), entry
