@@ -376,6 +376,30 @@ int miseg_surface_stats(void* stream, const int64_t* pred, const int64_t* target
                         int64_t* stats,     /* [N, n_classes, 2, 4] : n, max_sq, qlo_sq, qhi_sq */
                         double*  sum_dist,  /* [N, n_classes, 2]    : sum of sqrt(sq) over the n border pixels */
                         void* ws, int64_t ws_bytes);
+/* Per-sample affine warp of an fp32 batch and its exact adjoint; ref contrastyou/augment/tensor_affine_transform.py:68-78
+ * (AffineTensorTransform._perform_affine_transform: F.affine_grid + F.grid_sample, align_corners=True, padding_mode="zeros"; the
+ * inverse=True replay at :99-101).  x, y (gy, gx) are [N,C,H,W]-indexed: contiguous [N][C][H][W] when channels_last = 0,
+ * [N][H][W][C] when 1; theta is a DEVICE float[N][2][3], one matrix t per sample; mode 0 = bilinear, 1 = nearest.
+ * Output pixel (i, j) reads the source point
+ *   sx = (t00 xn + t01 yn + t02 + 1) / 2 * (W - 1),   sy = (t10 xn + t11 yn + t12 + 1) / 2 * (H - 1),
+ * with xn = 2 j / (W - 1) - 1, yn = 2 i / (H - 1) - 1 (torch's base grid; 0 along an axis of length 1).  Bilinear: the four
+ * neighbours (x', y') weighted (1 - |sx - x'|)(1 - |sy - y'|); nearest: the pixel (nearbyint(sx), nearbyint(sy)), ties to even.  A
+ * neighbour outside the image contributes 0.  No grid is written.  Any matrix is accepted: every read is bounds-checked, and a source
+ * point that is not finite reads nothing (that output pixel is 0).
+ * bwd is the adjoint with the forward's own weights w_n(p, q) (recomputed by the same device code, compiled without contraction):
+ *   gx[n,c,q] = sum_p w_n(p, q) gy[n,c,p],
+ * a gather: the owner of input pixel q scans, in row-major order, the output pixels within `reach` (per axis) of q's pre-image,
+ * rounded to a pixel and clamped into the image.  No atomics: two calls return the same bits.  The CALLER guarantees that reach
+ * covers the matrices: with A the 2x2 linear part of p -> s(p) in pixels (rows (t00, t01 (W-1)/(H-1)) and (t10 (H-1)/(W-1), t11); the
+ * row and column of an axis of length 1 replaced by the identity's), ceil(largest row sum of |A^-1|) + 1 suffices, and so does
+ * max(H, W) - 1 for any matrix, a singular one included (the box is then the whole image).  Pixels further away are not looked at.
+ * N, C >= 1, 1 <= H, W <= 2048, fewer than 2^31 elements, 1 <= reach <= 8; anything else, or a null pointer, returns MISEG_E_INVALID
+ * and launches nothing.  miseg_affine_warp_supported: 1 for a (C, H, W, channels_last, mode) the two calls take, else -1. */
+int64_t miseg_affine_warp_supported(int64_t C, int64_t H, int64_t W, int channels_last, int mode);
+int miseg_affine_warp_fwd(void* stream, const float* x, const float* theta, int64_t N, int64_t C, int64_t H, int64_t W,
+                          int channels_last, int mode, float* y);
+int miseg_affine_warp_bwd(void* stream, const float* gy, const float* theta, int64_t N, int64_t C, int64_t H, int64_t W,
+                          int channels_last, int mode, int64_t reach, float* gx);
 
 /* The iteration's scalar report in one launch   ref: the .item() reads of semi_seg/epocher.py:115-121 and the inline
  * `if torch.isnan(loss): raise` / `assert simplex(..)` of iic_loss.py:28-29,132-133,184-186.

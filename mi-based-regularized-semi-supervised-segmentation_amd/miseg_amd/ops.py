@@ -1296,6 +1296,110 @@ def flip(x: Tensor, flips: Tensor) -> Tensor:
     return _Flip.apply(x, flips) if x.requires_grad else _flip_raw(x, flips)
 
 
+# ------------------------------------------------------------------------------------------ affine warp (csrc/affine.hip)
+_AFFINE_MODES = {"bilinear": 0, "nearest": 1}
+AFFINE_MAX_REACH = 8
+
+
+def affine_inverse(theta: Tensor) -> Tensor:
+    """The [N, 2, 3] matrices of the inverse maps: ``[[A | t], [0 0 1]]`` inverted on the host in float64, as float32 on the CPU."""
+    t = theta.detach().to("cpu", torch.float64)
+    full = torch.zeros(t.shape[0], 3, 3, dtype=torch.float64)
+    full[:, :2] = t
+    full[:, 2, 2] = 1.0
+    try:
+        inv = torch.linalg.inv(full)
+    except RuntimeError as e:                # torch.linalg.LinAlgError is one
+        raise ValueError(f"affine_warp: inverse=True needs invertible matrices ({e})") from None
+    return inv[:, :2].to(torch.float32).contiguous()
+
+
+def affine_reach(theta: Tensor, h: int, w: int) -> int:
+    """The ``reach`` that ``miseg_affine_warp_bwd`` needs for these matrices on an ``h`` x ``w`` image (include/miseg_hip.h), from a host
+    copy in float64: ceil(largest row sum of |A^-1|) + 1 over the batch, A the linear part in pixels, or ``max(h, w) - 1`` (the whole
+    image) if that is smaller.  A singular matrix, or one so large that the forward's fp32 source points stray by a quarter of a pixel
+    of the pre-image (|theta| row sums ~1e3 at 2048 pixels), counts as needing the whole image.  The result may exceed
+    ``AFFINE_MAX_REACH``: the caller decides what to do then."""
+    t = theta.detach().to("cpu", torch.float64)
+    h, w = int(h), int(w)
+    both = h > 1 and w > 1
+    a00 = t[:, 0, 0] if w > 1 else torch.ones_like(t[:, 0, 0])
+    a11 = t[:, 1, 1] if h > 1 else torch.ones_like(t[:, 0, 0])
+    a01 = t[:, 0, 1] * ((w - 1) / (h - 1)) if both else torch.zeros_like(a00)
+    a10 = t[:, 1, 0] * ((h - 1) / (w - 1)) if both else torch.zeros_like(a00)
+    det = (a00 * a11 - a01 * a10).abs()
+    rowsum = torch.maximum(a11.abs() + a01.abs(), a10.abs() + a00.abs()) / det
+    stray = rowsum * 2.0 ** -21 * (t.abs().sum(2).amax(1) + 1.0) * max(h, w)
+    need = torch.where(torch.isfinite(rowsum) & (stray <= 0.25), torch.ceil(rowsum) + 1.0, torch.full_like(rowsum, float("inf")))
+    return int(max(1.0, min(float(need.max()), float(max(h, w) - 1))))
+
+
+class _AffineWarp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, theta: Tensor, mode: int, channels_last: bool, reach: Optional[int]):
+        n, c, h, w = x.shape
+        y = torch.empty_like(x)
+        call("miseg_affine_warp_fwd", _stream(), _ptr(x), _ptr(theta), n, c, h, w, int(channels_last), mode, _ptr(y))
+        ctx.save_for_backward(theta)
+        ctx.meta = (n, c, h, w, mode, channels_last, reach)
+        return y
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (theta,) = ctx.saved_tensors
+        n, c, h, w, mode, channels_last, reach = ctx.meta
+        g = g.float().contiguous(memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+        gx = torch.empty_like(g)
+        call("miseg_affine_warp_bwd", _stream(), _ptr(g), _ptr(theta), n, c, h, w, int(channels_last), mode, reach, _ptr(gx))
+        return gx, None, None, None, None
+
+
+def affine_warp(x: Tensor, theta: Tensor, mode: str = "bilinear", inverse: bool = False, reach: Optional[int] = None) -> Tensor:
+    """``F.grid_sample(x, F.affine_grid(theta, x.shape, align_corners=True), mode, "zeros", align_corners=True)`` for a GPU fp32
+    ``x`` [N, C, H, W], contiguous or channels_last (the output has the input's memory format), without the grid; the backward is
+    the exact adjoint as a gather, bit-reproducible (include/miseg_hip.h, miseg_affine_warp_fwd / _bwd).  ``theta`` [N, 2, 3] on the
+    CPU (uploaded) or on the device; no gradient flows to it.  ``inverse``: warp by the inverse maps (``affine_inverse``; a device
+    ``theta`` is read back for it).  ``reach``: the backward's search radius in pixels, 1..8; ``None`` computes it from the host copy
+    of the matrices (``affine_reach``) and takes 8 for a device ``theta``, whose matrices the caller then vouches for.  Raises
+    ``ValueError`` for anything the kernels do not take, and for matrices whose gradient they cannot cover when ``x`` requires one."""
+    if not isinstance(x, Tensor) or not isinstance(theta, Tensor):
+        raise ValueError("affine_warp: x and theta must be tensors")
+    if not x.is_cuda:
+        raise ValueError("affine_warp: x must be a GPU tensor (AffineTensorTransform takes CPU tensors through torch)")
+    if x.dtype != torch.float32 or x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"affine_warp: x must be a non-empty fp32 [N, C, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    if mode not in _AFFINE_MODES:
+        raise ValueError(f"affine_warp: mode must be one of {sorted(_AFFINE_MODES)}, got {mode!r}")
+    if theta.requires_grad:
+        raise ValueError("affine_warp: no gradient with respect to theta; pass theta.detach()")
+    n, c, h, w = x.shape
+    if tuple(theta.shape) != (n, 2, 3) or not theta.is_floating_point():
+        raise ValueError(f"affine_warp: theta must be a floating-point [{n}, 2, 3] tensor, got {tuple(theta.shape)}")
+    if x.is_contiguous():
+        channels_last = False
+    elif x.is_contiguous(memory_format=torch.channels_last):
+        channels_last = True
+    else:
+        raise ValueError("affine_warp: x must be contiguous or channels_last")
+    if _cabi.lib().miseg_affine_warp_supported(c, h, w, int(channels_last), _AFFINE_MODES[mode]) < 0 or x.numel() >= 2 ** 31:
+        raise ValueError(f"affine_warp: the kernels take 1 <= H, W <= 2048 and fewer than 2^31 elements, got {tuple(x.shape)}")
+    if reach is not None and not (isinstance(reach, int) and 1 <= reach <= AFFINE_MAX_REACH):
+        raise ValueError(f"affine_warp: reach must be an integer in 1..{AFFINE_MAX_REACH}, got {reach!r}")
+    needs_grad = x.requires_grad and torch.is_grad_enabled()
+    host = affine_inverse(theta) if inverse else (theta.detach() if not theta.is_cuda else None)
+    if host is not None:
+        need = affine_reach(host, h, w)
+        if needs_grad and need > (AFFINE_MAX_REACH if reach is None else reach):
+            raise ValueError(f"affine_warp: the backward would have to search {need} pixels around each pre-image for these matrices, "
+                             f"more than {'the limit of 8' if reach is None else f'reach={reach}'}; use torch's grid_sample for them")
+        reach = min(need, AFFINE_MAX_REACH) if reach is None else reach
+        theta = host
+    elif reach is None:
+        reach = AFFINE_MAX_REACH
+    theta = theta.detach().to(device=x.device, dtype=torch.float32).contiguous()
+    return _AffineWarp.apply(x, theta, _AFFINE_MODES[mode], channels_last, int(reach))
+
+
 def argmax_dice(logits: Tensor, labels: Optional[Tensor], want_pred: bool = True, to_host: bool = False):
     """argmax over channels and per-sample per-class (intersection, union) int64 counts.  ``to_host``: inside a training iteration,
     write the counts into the iteration's read-back block (``stepio``) so that they travel with its scalars."""
