@@ -376,6 +376,35 @@ int miseg_surface_stats(void* stream, const int64_t* pred, const int64_t* target
                         int64_t* stats,     /* [N, n_classes, 2, 4] : n, max_sq, qlo_sq, qhi_sq */
                         double*  sum_dist,  /* [N, n_classes, 2]    : sum of sqrt(sq) over the n border pixels */
                         void* ws, int64_t ws_bytes);
+/* Keep the largest connected component of each listed class of a class-coded mask pred (int64 [N,H,W]).  The reference project has
+ * no post-processing: the definition is this project's own, pinned to scipy.ndimage.label + np.bincount.
+ * Units: rank 2 = every slice is a unit of its own; rank 3 = the N slices are one volume.  Pixel index inside a unit: y * W + x
+ * (rank 2), (n * H + y) * W + x (rank 3).  connectivity 1 = face neighbours (4 / 6), 2 = the full neighbourhood (8 / 26);
+ * outside the image is outside every component.  A component is a maximal connected set of pixels of one unit with the same
+ * listed class value.  Kept per (unit, class): the component with the most pixels, among equals the one that holds the smallest
+ * pixel index (np.argmax(np.bincount(lab.ravel())[1:]) + 1 on scipy's labels).
+ *   out    [N,H,W] int64 = pred with every pixel of a listed class outside its kept component replaced by fill; pixels whose value
+ *          is not listed are copied.  out may be pred.
+ *   labels [N,H,W] int32, or NULL: the smallest pixel index (inside its unit) of the pixel's component; -1 for a value not listed.
+ *   stats  [U, n_classes, 3] int64, U = N (rank 2) or 1 (rank 3): components, pixels of the kept one, pixels of the class; a class
+ *          absent from a unit gives (0, 0, 0).
+ *   target [N,H,W] int64, or NULL; with it inter, uni [N, C] int64 are filled for out against target as miseg_argmax_dice defines
+ *          them: inter = #(out == c and target == c), uni = #(out == c) + #(target == c); values outside [0, C) count in nothing.
+ * classes is a DEVICE int32[n_classes], as in miseg_surface_stats: the host cannot see its values, so every content is accepted and
+ * is memory-safe, with this meaning: an entry outside [0, 64) or equal to fill lists nothing, and of equal entries the first one
+ * lists the class (the others report (0, 0, 0)).  A caller that holds the list on the host checks it there
+ * (miseg_amd.ops.largest_component raises for an entry out of range, a duplicate and fill in the list).
+ * Integer atomics only (minimum, maximum, add), no floating point: two calls return the same bits in every output.  Every loop
+ * follows labels that strictly decrease; nothing waits for another thread; the phases are separate launches.
+ * N >= 1, 1 <= H, W <= 2048, fewer than 2^31 pixels, 1 <= n_classes <= 64, rank 2 or 3, connectivity 1 or 2, 0 <= fill < 64,
+ * 1 <= C <= 64 with a target; anything else, a null required pointer or a short workspace returns MISEG_E_INVALID and launches
+ * nothing (the size query returns -1 for a bad shape). */
+int64_t miseg_largest_component_ws_bytes(int64_t N, int64_t H, int64_t W, int64_t n_classes, int rank);
+int miseg_largest_component(void* stream, const int64_t* pred, int64_t N, int64_t H, int64_t W,
+                            const int32_t* classes /* device */, int64_t n_classes, int rank, int connectivity, int64_t fill,
+                            int64_t* out, int32_t* labels /* or NULL */, int64_t* stats,
+                            const int64_t* target /* or NULL */, int64_t C, int64_t* inter, int64_t* uni,
+                            void* ws, int64_t ws_bytes);
 /* Per-sample affine warp of an fp32 batch and its exact adjoint; ref contrastyou/augment/tensor_affine_transform.py:68-78
  * (AffineTensorTransform._perform_affine_transform: F.affine_grid + F.grid_sample, align_corners=True, padding_mode="zeros"; the
  * inverse=True replay at :99-101).  x, y (gy, gx) are [N,C,H,W]-indexed: contiguous [N][C][H][W] when channels_last = 0,

@@ -92,6 +92,16 @@ def write_predict(predict_logit, save_dir: str, filenames):
         _write_single_png(m, os.path.join(save_dir, "pred"), f)
 
 
+def write_prediction_map(pred, save_dir: str, filenames, folder: str):
+    """Class-coded maps [N, H, W] (a prediction after post-processing) as PNGs under ``save_dir/folder``, named like ``pred/``'s."""
+    import os
+    assert len(pred.shape) == 3, pred.shape
+    filenames = [filenames] if isinstance(filenames, str) else filenames
+    assert len(filenames) == len(pred)
+    for m, f in zip(pred.detach().cpu(), filenames):
+        _write_single_png(m, os.path.join(save_dir, folder), f)
+
+
 def write_img_target(image, target, save_dir: str, filenames):
     import os
     filenames = [filenames] if isinstance(filenames, str) else filenames

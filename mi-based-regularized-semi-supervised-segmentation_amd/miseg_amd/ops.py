@@ -1447,6 +1447,45 @@ def surface_stats(pred: Tensor, target: Tensor, classes: Sequence[int], q: float
     return stats, sum_dist
 
 
+def largest_component(pred: Tensor, classes: Sequence[int], volume: bool = False, connectivity: int = 1, fill: int = 0,
+                      target: Optional[Tensor] = None, num_classes: Optional[int] = None, want_labels: bool = False,
+                      ws: Optional[Tensor] = None, out: Optional[Tensor] = None):
+    """Keep the largest connected component of each class in ``classes`` of the class-coded ``pred`` (int64 [N, H, W]); every other
+    pixel of those classes becomes ``fill`` (include/miseg_hip.h, miseg_largest_component, has the definition: scipy.ndimage.label's,
+    ties to the component with the first pixel).  ``volume``: the N slices are one 3-D unit instead of N 2-D ones; ``connectivity`` 1 =
+    faces, 2 = the full neighbourhood.  Returns ``(out, stats)`` with ``stats`` int64 [U, len(classes), 3] = (components, pixels kept,
+    pixels of the class); then ``labels`` (int32 [N, H, W], the first pixel index of the pixel's component, -1 elsewhere) if
+    ``want_labels``; then ``(inter, uni)`` (int64 [N, num_classes], ``argmax_dice``'s counts of ``out`` against ``target``) if a target
+    is given.  ``out`` may be ``pred`` itself.  One library call, no host sync.  CPU tensors, and every tensor with
+    ``MISEG_COMPONENTS_HOST=1``, take the scipy twin (``miseg_amd.components``); ``MISEG_COMPONENTS_HOST=0`` refuses CPU tensors.
+    Every bad argument is a ValueError, never a RuntimeError, which ``InferenceEpocher`` would take for an absent class."""
+    from . import components as host
+    mode = os.environ.get("MISEG_COMPONENTS_HOST")
+    cls, fill, c = host.check_arguments(pred, classes, connectivity, fill, target, num_classes, out)
+    if not pred.is_cuda or mode == "1":
+        if not pred.is_cuda and mode == "0":
+            raise ValueError("largest_component: CPU tensors with MISEG_COMPONENTS_HOST=0 (the host path is switched off)")
+        return host.largest_component_host(pred, cls, volume, connectivity, fill, target, num_classes, want_labels, None, out)
+    n, h, w = pred.shape
+    dev = pred.device
+    pred = pred.contiguous()
+    rank = 3 if volume else 2
+    cls_dev = cached_const(("component_classes", str(dev), cls), lambda: torch.tensor(cls, dtype=torch.int32, device=dev))
+    out = torch.empty_like(pred) if out is None else out
+    labels = torch.empty(n, h, w, dtype=torch.int32, device=dev) if want_labels else None
+    stats = torch.empty(1 if volume else n, len(cls), 3, dtype=torch.int64, device=dev)
+    inter = uni = None
+    if target is not None:
+        target = target.contiguous()
+        block = torch.empty(2, n, c, dtype=torch.int64, device=dev)
+        inter, uni = block[0], block[1]
+    if ws is None:
+        ws = _ws(query("miseg_largest_component_ws_bytes", n, h, w, len(cls), rank), dev)
+    call("miseg_largest_component", _stream(), _ptr(pred), n, h, w, _ptr(cls_dev), len(cls), rank, int(connectivity), fill, _ptr(out),
+         _ptr(labels), _ptr(stats), _ptr(target), c, _ptr(inter), _ptr(uni), _ptr(ws), ws.numel())
+    return host.pack(out, stats, labels, None if target is None else (inter, uni))
+
+
 # ------------------------------------------------------------------------------------------ split with a layout-preserving backward
 _SPLIT_MEMCPY = False   # True: assemble slice gradients with hipMemcpy (slower on a busy device)
 

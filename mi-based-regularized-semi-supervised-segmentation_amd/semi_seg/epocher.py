@@ -26,7 +26,8 @@ from torch import Tensor, nn
 
 from contrastyou.epocher._utils import preprocess_input_with_single_transformation  # noqa
 from contrastyou.epocher._utils import preprocess_input_with_twice_transformation  # noqa
-from contrastyou.epocher._utils import GlobalLabelGenerator, LocalLabelGenerator, write_img_target, write_predict
+from contrastyou.epocher._utils import (GlobalLabelGenerator, LocalLabelGenerator, write_img_target, write_predict,
+                                        write_prediction_map)
 from contrastyou.helper import average_iter, weighted_average_iter
 from contrastyou.trainer._utils import ClusterHead  # noqa
 from deepclustering2.augment.tensor_augment import TensorRandomFlip
@@ -224,13 +225,22 @@ class InferenceEpocher(EvalEpocher):
     """Evaluation that also dumps image / ground truth / prediction PNGs and reports per-class surface distances
     (ref :76-107): ``surface_metrics`` lists ``SurfaceMeter`` names, registered as ``hd`` (hausdorff, the reference's one),
     ``mhd`` (mod_hausdorff) and ``asd`` (average_surface).  The argmax + Dice counts stay fused on the device and so do the surface
-    statistics (one ``miseg_surface_stats`` launch per batch, shared by the meters); the PNG writes are host work, as in the reference."""
+    statistics (one ``miseg_surface_stats`` launch per batch, shared by the meters); the PNG writes are host work, as in the reference.
+
+    ``keep_largest`` (default off: every report, key and file is then what it is without it) adds the same measurements on the
+    prediction with only the largest connected component of each foreground class kept, per slice (a loader batch need not be a
+    whole patient, so not per volume): one ``ops.largest_component`` call per batch, which also returns the cleaned prediction's Dice
+    counts.  The meters ``dice_lcc`` and ``hd_lcc`` / ``mhd_lcc`` / ``asd_lcc`` stand next to the raw prediction's, which stay, and
+    the cleaned maps go to ``pred_lcc/``.  ``component_connectivity``: 1 = 4-neighbours, 2 = 8-neighbours."""
 
     SURFACE_METERS = {"hausdorff": "hd", "mod_hausdorff": "mhd", "average_surface": "asd"}
 
-    def __init__(self, model, val_loader: T_loader, sup_criterion: T_loss, cur_epoch=0, device="cpu", surface_metrics=("hausdorff",)) -> None:
+    def __init__(self, model, val_loader: T_loader, sup_criterion: T_loss, cur_epoch=0, device="cpu", surface_metrics=("hausdorff",),
+                 keep_largest=False, component_connectivity=1) -> None:
         self._surface_metrics = tuple(surface_metrics)
         assert all(m in self.SURFACE_METERS for m in self._surface_metrics), surface_metrics
+        assert component_connectivity in (1, 2), component_connectivity
+        self._keep_largest, self._component_connectivity = bool(keep_largest), int(component_connectivity)
         super().__init__(model, val_loader, sup_criterion, cur_epoch=cur_epoch, device=device)
 
     def set_save_dir(self, save_dir):
@@ -241,7 +251,22 @@ class InferenceEpocher(EvalEpocher):
         for metername in self._surface_metrics:
             meters.register_meter(self.SURFACE_METERS[metername],
                                   SurfaceMeter(C=self.num_classes, report_axises=list(range(1, self.num_classes)), metername=metername))
+        if self._keep_largest:
+            meters.register_meter("dice_lcc", UniversalDice(self.num_classes, report_axises=list(range(1, self.num_classes))))
+            for metername in self._surface_metrics:
+                meters.register_meter(self.SURFACE_METERS[metername] + "_lcc",
+                                      SurfaceMeter(C=self.num_classes, report_axises=list(range(1, self.num_classes)), metername=metername))
         return meters
+
+    def _add_surface(self, pred, labels, suffix=""):
+        shared = None                              # the batch's surface statistics: one launch for all the surface meters
+        if len(self._surface_metrics) > 1 and SurfaceMeter.on_device(pred, labels):
+            shared = SurfaceMeter.batch_stats(pred, labels, list(range(1, self.num_classes)))
+        for metername in self._surface_metrics:
+            try:                                   # ref: ExceptionIgnorer(RuntimeError) -- a class absent from a slice
+                self.meters[self.SURFACE_METERS[metername] + suffix].add(pred, labels, stats=shared)
+            except RuntimeError:
+                pass
 
     @torch.no_grad()
     def _run(self, *args, **kwargs) -> Tuple[EpochResultDict, float]:
@@ -260,14 +285,14 @@ class InferenceEpocher(EvalEpocher):
             pred, inter, union = ops.argmax_dice(val_logits, labels, want_pred=True)
             self.meters["loss"].add(val_loss.item())
             self.meters["dice"].add_counts(inter, union, group_name=group)
-            shared = None                          # the batch's surface statistics: one launch for all the surface meters
-            if len(self._surface_metrics) > 1 and SurfaceMeter.on_device(pred, labels):
-                shared = SurfaceMeter.batch_stats(pred, labels, list(range(1, self.num_classes)))
-            for metername in self._surface_metrics:
-                try:                               # ref: ExceptionIgnorer(RuntimeError) -- a class absent from a slice
-                    self.meters[self.SURFACE_METERS[metername]].add(pred, labels, stats=shared)
-                except RuntimeError:
-                    pass
+            self._add_surface(pred, labels)
+            if self._keep_largest:
+                cleaned, _, (inter_lcc, union_lcc) = ops.largest_component(
+                    pred, list(range(1, self.num_classes)), volume=False, connectivity=self._component_connectivity, fill=0,
+                    target=labels.contiguous().long(), num_classes=self.num_classes)
+                self.meters["dice_lcc"].add_counts(inter_lcc, union_lcc, group_name=group)
+                self._add_surface(cleaned, labels, "_lcc")
+                write_prediction_map(cleaned, self._save_dir, file_path, "pred_lcc")
             report_dict = self.meters.tracking_status()
             self._indicator.set_postfix_dict(report_dict)
         return report_dict, self.meters["dice"].summary()["DSC_mean"]

@@ -162,18 +162,25 @@ class SemiTrainer(Trainer):
     def _inference_model(self) -> nn.Module:
         return self._model
 
-    def inference(self, checkpoint=None, surface_metrics=None):  # noqa
+    def inference(self, checkpoint=None, surface_metrics=None, keep_largest=None):  # noqa
         """``surface_metrics``: ``SurfaceMeter`` names to report (``hausdorff`` -> ``hd``, ``mod_hausdorff`` -> ``mhd``,
         ``average_surface`` -> ``asd``); None reads the optional ``Inference.surface_metrics`` of the configuration, whose default is
-        the reference's ``("hausdorff",)``."""
+        the reference's ``("hausdorff",)``.  ``keep_largest``: also report the prediction with only the largest connected component
+        of each foreground class kept (``InferenceEpocher``: the ``*_lcc`` meters and ``pred_lcc/``); None reads the optional
+        ``Inference.keep_largest_component`` (default false) and ``Inference.component_connectivity`` (default 1).  The returned
+        score is the raw prediction's DSC_mean either way."""
         if checkpoint is not None and not Path(checkpoint).exists():
             raise AssertionError(checkpoint)         # the reference asserts the path (semi_seg/trainer.py:112-115) before resolving it
         target = _checkpoint_file(checkpoint, self._save_dir)
         self.load_state_dict_from_path(str(target), strict=True)
         if surface_metrics is None:
             surface_metrics = (self._config.get("Inference") or {}).get("surface_metrics") or ("hausdorff",)
+        if keep_largest is None:
+            keep_largest = bool((self._config.get("Inference") or {}).get("keep_largest_component", False))
+        connectivity = int((self._config.get("Inference") or {}).get("component_connectivity", 1))
         runner = E.InferenceEpocher(self._inference_model(), val_loader=self._test_loader, sup_criterion=self._sup_criterion,
-                                    cur_epoch=self._cur_epoch, device=self._device, surface_metrics=tuple(surface_metrics))
+                                    cur_epoch=self._cur_epoch, device=self._device, surface_metrics=tuple(surface_metrics),
+                                    keep_largest=bool(keep_largest), component_connectivity=connectivity)
         runner.set_save_dir(self._save_dir)
         return runner.run()
 
