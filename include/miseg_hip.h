@@ -539,7 +539,10 @@ int miseg_bn_relu_fwd(void* stream, int dt, const void* raw, int64_t N, int64_t 
  * bit-reproducible; a block sum of 2^30 or more, or a non-finite one, is counted in acc[2 Cout] and the layer's statistics then come out
  * NaN).  Shapes: miseg_conv3x3_fwd_acc_supported (Cout <= 256, at most 2 048 blocks: the no-wrap bound).  miseg_bn_relu_fwd_acc =
  * miseg_bn_finalize + miseg_bn_relu_fwd: every block turns the totals into scale / shift itself, block 0 writes `saved`
- * ([mean | invstd | scale | shift], what the backward reads) and moves running_mean / running_var / num_batches_tracked.  C <= 256. */
+ * ([mean | invstd | scale | shift], what the backward reads) and moves running_mean / running_var / num_batches_tracked.  C <= 256.
+ * Frozen statistics: miseg_bn_finalize, miseg_bn_relu_fwd_acc and miseg_conv3x3_bn_fwd called with running_mean == running_var ==
+ * num_batches_tracked == NULL normalise with the batch statistics and write the same `saved` and outputs, and touch none of the three
+ * (a training-mode forward with track_running_stats switched off: the perturbed passes of virtual adversarial training). */
 /* The stem convolution and its weight gradient without matrix cores (ref contrastyou/arch/unet.py:58: `conv_block(input_dim = 1, 16)`'s
  * first Conv2d): x = [N][H][W][CP] whose channel 0 is the image -- in 16-bit storage (the padded channel vector the other entry points
  * take; x_f32 = 0) or the fp32 image itself (x_f32 = 1, CP = 1: rounded to the storage type as it is read, so the padded copy need
@@ -552,6 +555,18 @@ int miseg_conv3x3_stem_fwd(void* stream, int dt, const void* x, int x_f32, int64
 int64_t miseg_conv3x3_stem_wgrad_ws_bytes(int64_t Cout);
 int miseg_conv3x3_stem_wgrad(void* stream, int dt, const void* x, int x_f32, int64_t CP, int64_t N, int64_t H, int64_t W, const void* graw,
                              int64_t Cout, float* gw, void* ws, int64_t ws_bytes);
+/* The stem's DATA gradient (the gradient of a loss with respect to a one-channel input image: virtual adversarial training, saliency
+ * maps): gimage[n,y,x] = sum_k sum_{dy,dx} graw[n, y+1-dy, x+1-dx, k] * w[k,0,dy,dx], zero outside the image.  graw = NHWC [N][H][W][Cout]
+ * of `dt` (fp32, bf16, fp16), w = the fp32 master weight [Cout][1][3][3], rounded to `dt` as miseg_conv3x3_stem_fwd rounds it; fp32
+ * accumulation in a fixed order (two calls give the same bits); gimage = fp32 [N][1][H][W].  A thread owns a pixel column of a run of
+ * image rows: every graw row is read once per block (9 Cout multiply-adds per pixel), the nine tap sums of a row cross the lanes
+ * through LDS.  Shapes: miseg_conv3x3_stem_dgrad_supported (Cout a multiple of one 16-byte vector, Cout <= 64, W <= 1022); anything else
+ * goes through miseg_conv3x3_fwd over a dgrad-packed (kind 1) weight whose input channels are zero-padded to one vector -- channel 0 of
+ * that result is this gradient, rounded to `dt`.  ws (miseg_conv3x3_stem_dgrad_ws_bytes) holds the rounded weights. */
+int64_t miseg_conv3x3_stem_dgrad_supported(int dt, int64_t Cout, int64_t W);
+int64_t miseg_conv3x3_stem_dgrad_ws_bytes(int64_t Cout);
+int miseg_conv3x3_stem_dgrad(void* stream, int dt, const void* graw, int64_t N, int64_t H, int64_t W, int64_t Cout, const float* w,
+                             float* gimage, void* ws, int64_t ws_bytes);
 int64_t miseg_conv3x3_fwd_acc_supported(int dt, int64_t Cin, int64_t N, int64_t H, int64_t W, int64_t Cout);
 int miseg_conv3x3_fwd_acc(void* stream, int dt, const void* in0, int64_t C0, int ups0, const void* in1, int64_t C1, int ups1,
                           int64_t N, int64_t H, int64_t W, const void* packed_w, int64_t Cout, void* out, void* acc);
@@ -783,6 +798,26 @@ int miseg_bias_amaxpool_fwd(void* stream, int dt, const void* raw, int64_t N, in
                             int64_t OH, int64_t OW, int64_t PH, int64_t PW, int64_t V, float* e, int32_t* idx);
 int miseg_bias_amaxpool_bwd(void* stream, int dt, const float* ge, const int32_t* idx, int64_t N, int64_t H, int64_t W, int64_t C,
                             int64_t OH, int64_t OW, int64_t PH, int64_t PW, int64_t V, void* graw, float* gbias);
+
+/* ------------------------------------------------------------------------------------------
+ * Virtual adversarial training (Trainer.name=vat; csrc/vat.hip)   ref: whl:deepclustering2/utils/VAT.py (_l2_normalize, VATLoss:
+ * `torch.randn_like(x)`, `d /= norm`, `x + xi * d`, `x + d * eps * prop_eps`).  fp32 tensors of N samples with M elements each.
+ * l2_perturb : per sample n, s = ||g_n||_2 (squares and their sum in double, a fixed order: two calls give the same bits), then
+ *              d_n = g_n / s, r_n = scale[n] * d_n, out_n = x_n + r_n (one fp32 division, one multiply, one add per element, not
+ *              contracted).  scale = device fp32 [N].  out, r and d may each be NULL (at least one is not); x may be NULL when out is;
+ *              no output may alias an input.  A sample whose s is zero or not finite -- the reference's `allclose(norm, 1)` assertion fails there --
+ *              adds 1 to flag[0] (int32, zero before the first call that shares it) and gets d_n = r_n = 0, out_n = x_n: no NaN is written.
+ *              ws from miseg_l2_perturb_ws_bytes.  M <= 2^30.
+ * normal_fill: out[i] = a standard normal that depends on (seed, offset + i) alone, never on the launch geometry: element j = offset + i
+ *              takes word j & 3 of Philox4x32-10(counter = (lo32(j >> 2), hi32(j >> 2), 0, 0), key = (lo32(seed), hi32(seed))); words
+ *              (0, 1) and (2, 3) are Box-Muller pairs: u1 = ((a >> 8) + 1) * 2^-24 in (0, 1], u2 = (b >> 8) * 2^-24,
+ *              z = sqrt(-2 ln u1) * (cos | sin)(2 pi u2).  miseg_philox_fill writes the 32-bit words themselves (int32 bit patterns).
+ * ------------------------------------------------------------------------------------------ */
+int64_t miseg_l2_perturb_ws_bytes(int64_t N, int64_t M);
+int miseg_l2_perturb(void* stream, const float* g, const float* x, const float* scale, int64_t N, int64_t M, float* out, float* r,
+                     float* d, int32_t* flag, void* ws, int64_t ws_bytes);
+int miseg_normal_fill(void* stream, int64_t seed, int64_t offset, float* out, int64_t numel);
+int miseg_philox_fill(void* stream, int64_t seed, int64_t offset, int32_t* out, int64_t numel);
 
 #ifdef __cplusplus
 }

@@ -299,6 +299,84 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const TX* __restrict__ 
 __global__ __launch_bounds__(256) void stem_wgrad_sum_kernel(const float* __restrict__ partials, int nparts, int len, float* __restrict__ gw) {
     reduce_partials_block(partials, nparts, (size_t)len, len, gw, [](int e) { return (size_t)e; });
 }
+// ---- the stem's data gradient: gimage[n,y,x] = sum_k sum_{dy,dx} graw[n, y+1-dy, x+1-dx, k] * w[k,0,dy,dx] (fp32 [N][1][H][W]).
+// The same walk as the two kernels above -- a block owns a run of image rows (row = n * H + h), a thread the pixel columns
+// threadIdx.x + 256 k -- turned around: for every INPUT row r of graw (the run and one row either side) a thread reads its pixel's Cout
+// values once, in 16-byte vectors, and forms the nine tap sums T[dy][dx] = sum_k graw[r, x, k] * w[k, dy, dx] (weights rounded to the
+// storage type beforehand, read through uniform loads); the sums cross the lanes through LDS (R[dy][x] = sum_dx T[dy][dx][x + 1 - dx],
+// a zero column either side), and row r's R[dy] is added to output row r - 1 + dy where that row belongs to the same image.  Three
+// running rows of accumulators per column; output row r - 1 is complete, and stored, once input row r has been added.  Sums in a fixed
+// order: k ascending inside a tap, dx ascending, then dy = 2, 1, 0.
+template <typename T>
+__global__ void stem_dgrad_round_w_kernel(const float* __restrict__ w, int n, float* __restrict__ wr) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) wr[i] = to_f32(from_f32<T>(w[i]));
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const T* __restrict__ graw, int N, int H, int W, int Cout, const float* __restrict__ wr,
+                                                         float* __restrict__ gimage) {
+    constexpr int V = VT<T>::V;
+    typedef typename VT<T>::Raw Raw;
+    extern __shared__ float stem_taps[];                 // [9][W + 2]: column x lives at x + 1, columns 0 and W + 1 stay zero
+    const int RB = W + 2, rows = N * H, per = (rows + (int)gridDim.x - 1) / (int)gridDim.x, CV = Cout / V;
+    const int r_begin = blockIdx.x * per, r_end = min(rows, r_begin + per);
+    if (r_begin >= r_end) return;
+    for (int i = threadIdx.x; i < 9 * RB; i += 256) stem_taps[i] = 0.f;
+    float prev[kStemPre], cur[kStemPre], next[kStemPre];     // output rows r - 1, r, r + 1 while input row r is added
+#pragma unroll
+    for (int k = 0; k < kStemPre; ++k) prev[k] = cur[k] = next[k] = 0.f;
+    for (int r = r_begin - 1; r <= r_end; ++r) {
+        const bool live = r >= 0 && r < rows;            // block-uniform
+        const int h = live ? r % H : 0;
+        __syncthreads();                                 // the readers of the previous row's sums (first pass: the zero fill) are done
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < kStemPre; ++k) {
+                const int x = (int)threadIdx.x + 256 * k;
+                if (x >= W) continue;
+                float t[9];
+#pragma unroll
+                for (int tap = 0; tap < 9; ++tap) t[tap] = 0.f;
+                const Raw* gp = reinterpret_cast<const Raw*>(graw + ((size_t)r * W + x) * Cout);
+                for (int cv = 0; cv < CV; ++cv) {
+                    float f[V];
+                    VT<T>::unpack(gp[cv], f);
+#pragma unroll
+                    for (int i = 0; i < V; ++i) {
+                        const float* wk = wr + (cv * V + i) * 9;
+#pragma unroll
+                        for (int tap = 0; tap < 9; ++tap) t[tap] = fmaf(f[i], wk[tap], t[tap]);
+                    }
+                }
+#pragma unroll
+                for (int tap = 0; tap < 9; ++tap) stem_taps[tap * RB + x + 1] = t[tap];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kStemPre; ++k) {
+            const int x = (int)threadIdx.x + 256 * k;
+            if (x >= W) continue;
+            if (live) {
+                float R[3];
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int dx = 0; dx < 3; ++dx) s += stem_taps[(dy * 3 + dx) * RB + (x + 1 - dx) + 1];
+                    R[dy] = s;
+                }
+                if (h >= 1) prev[k] += R[0];             // output row r - 1 reads this row with dy = 0 (same image only)
+                cur[k] += R[1];
+                if (h <= H - 2) next[k] += R[2];         // output row r + 1 reads it with dy = 2
+            }
+            if (r - 1 >= r_begin && r - 1 < r_end) gimage[(size_t)(r - 1) * W + x] = prev[k];
+            prev[k] = cur[k]; cur[k] = next[k]; next[k] = 0.f;
+        }
+    }
+}
+
 constexpr int kStemBlocksMax = 4096;
 static const int kStemBlocks = [] { const char* e = getenv("MISEG_STEM_BLOCKS"); return e ? std::min(kStemBlocksMax, std::max(1, atoi(e))) : 1024; }();      // (ws sized for kStemBlocksMax)
 
@@ -379,6 +457,35 @@ extern "C" int miseg_conv3x3_stem_wgrad(void* stream, int dt, const void* x, int
     const int len = (int)(Cout * 9);
     hipLaunchKernelGGL(stem_wgrad_sum_kernel, dim3(reduce_grid(len, nb)), dim3(256), 0, st, (const float*)ws, (int)nb, len, gw);
     MISEG_LAUNCH_CHECK("stem_wgrad_sum_kernel");
+    return MISEG_OK;
+}
+
+// ---- the stem's data gradient (see stem_dgrad_kernel): every storage type; Cout in whole 16-byte vectors
+extern "C" int64_t miseg_conv3x3_stem_dgrad_supported(int dt, int64_t Cout, int64_t W) {
+    if (dt != MISEG_F32 && dt != MISEG_BF16 && dt != MISEG_F16) return 0;
+    const int vec = dt == MISEG_F32 ? 4 : 8;
+    return Cout >= vec && Cout <= 64 && Cout % vec == 0 && W >= 1 && W + 2 <= 256 * kStemPre;
+}
+
+extern "C" int64_t miseg_conv3x3_stem_dgrad_ws_bytes(int64_t Cout) { return Cout > 0 ? Cout * 9 * 4 : 0; }
+
+extern "C" int miseg_conv3x3_stem_dgrad(void* stream, int dt, const void* graw, int64_t N, int64_t H, int64_t W, int64_t Cout, const float* w,
+                                        float* gimage, void* ws, int64_t ws_bytes) {
+    MISEG_TAPE(miseg_conv3x3_stem_dgrad, stream, dt, graw, N, H, W, Cout, w, gimage, ws, ws_bytes);
+    MISEG_F16_DISPATCH_ON(dt, miseg_conv3x3_stem_dgrad, stream, MISEG_BF16, graw, N, H, W, Cout, w, gimage, ws, ws_bytes);
+    MISEG_REQUIRE(graw && w && gimage && ws && N > 0 && H > 0 && W > 0 && N * H < (1LL << 31), "conv3x3_stem_dgrad: bad args");
+    MISEG_REQUIRE(miseg_conv3x3_stem_dgrad_supported(dt, Cout, W), "conv3x3_stem_dgrad: Cout in whole 16-byte vectors up to 64, rows of at most %d pixels "
+                  "(ask miseg_conv3x3_stem_dgrad_supported)", 256 * kStemPre - 2);
+    MISEG_REQUIRE(((uintptr_t)graw & 15) == 0 && ((uintptr_t)ws & 3) == 0 && ws_bytes >= miseg_conv3x3_stem_dgrad_ws_bytes(Cout),
+                  "conv3x3_stem_dgrad: graw must be 16-byte aligned, the workspace miseg_conv3x3_stem_dgrad_ws_bytes large");
+    const unsigned nb = (unsigned)std::min<int64_t>(N * H, (int64_t)kStemBlocks);
+    const int nw = (int)(Cout * 9);
+    hipStream_t st = as_stream(stream);
+    MISEG_WITH_STORAGE_TYPE(dt, "conv3x3_stem_dgrad",
+        hipLaunchKernelGGL(stem_dgrad_round_w_kernel<TT>, dim3((unsigned)cdiv(nw, 256)), dim3(256), 0, st, w, nw, (float*)ws);
+        hipLaunchKernelGGL(stem_dgrad_kernel<TT>, dim3(nb), dim3(256), (size_t)9 * (W + 2) * 4, st, (const TT*)graw, (int)N, (int)H, (int)W, (int)Cout,
+                           (const float*)ws, gimage));
+    MISEG_LAUNCH_CHECK("stem_dgrad_kernel");
     return MISEG_OK;
 }
 

@@ -7,6 +7,7 @@ ref: contrastyou/arch/unet.py:10-40 (conv_block / up_conv), :61-64 (pools), :84,
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 from typing import Optional, Tuple
@@ -159,8 +160,109 @@ def vec_of(dtype) -> int:
     return 8 if dtype in (torch.bfloat16, torch.float16) else 4
 
 
+# ---- gradients with respect to the input image, and forward passes that leave the running statistics alone (virtual adversarial
+# training; saliency maps and adversarial evaluation need the first too)
+# The stem's data gradient through its own pixel-per-thread kernel (miseg_conv3x3_stem_dgrad); 0: the generic path (the streaming /
+# tiled convolution over a dgrad-packed weight whose input channels are padded to one vector; channel 0 of its output).
+_STEM_DGRAD = os.environ.get("MISEG_STEM_DGRAD", "1") != "0"
+_bn_untracked = False
+_data_grad_only = False
+_bn_float_stats = False
+
+
+@contextlib.contextmanager
+def bn_untracked():
+    """Training-mode forwards inside this block normalise with the batch statistics and leave ``running_mean``, ``running_var`` and
+    ``num_batches_tracked`` untouched (``track_running_stats`` switched off, as the wheel's ``_disable_tracking_bn_stats`` does): the
+    BatchNorm kernels get null pointers for the three, which every forward variant -- accumulator, counter, finalize, stem -- takes as
+    "do not track".  Outputs and ``saved`` coefficients are those of a tracked pass.  Evaluation-mode forwards are not affected."""
+    global _bn_untracked
+    prev, _bn_untracked = _bn_untracked, True
+    try:
+        yield
+    finally:
+        _bn_untracked = prev
+
+
+@contextlib.contextmanager
+def bn_float_statistics():
+    """Training-mode forwards inside this block take their batch statistics from the float partial sums (one row per convolution
+    block + ``miseg_bn_finalize``, or the last-block counter form), not from the fixed-point accumulators: the path ``MISEG_BN_ACC=0``
+    selects, for these forwards only.  For computations that DIFFERENCE two forward passes of nearly the same input (VAT's direction at
+    a small ``xi``): with the accumulators the direction after one iteration at ``xi = 0.1`` was measured 1.6e-3 from the float64
+    reference, with the float sums 1.3e-4, where a float32 evaluation on the CPU lands at 9e-5."""
+    global _bn_float_stats
+    prev, _bn_float_stats = _bn_float_stats, True
+    try:
+        yield
+    finally:
+        _bn_float_stats = prev
+
+
+@contextlib.contextmanager
+def data_grad_only():
+    """Forwards inside this block build a graph whose backward DELIVERS data gradients only: no weight-gradient launch of the 3x3
+    convolutions, no flat-gradient slot claimed or written, ``param.grad`` untouched, no weight-gradient side stream.  Two sums are
+    still formed and dropped, into scratch: gamma's and beta's (the BatchNorm data gradient needs them anyway) and the 1x1 head's
+    weight and bias sums, which its one backward kernel forms in the pass that writes the data gradient (68 multiply-adds per pixel).  The flag is read when the
+    forward runs and travels in the node, so the backward may run after the block has been left (VAT's direction pass)."""
+    global _data_grad_only
+    prev, _data_grad_only = _data_grad_only, True
+    try:
+        yield
+    finally:
+        _data_grad_only = prev
+
+
+class _StemSink:
+    """Hand-over of the image gradient from the stem layer's backward to ``_StemInput``'s: the layer's input is the zero-padded
+    channel vector [B,VEC,H,W] of the storage type, the image's gradient is fp32 [B,1,H,W] -- ``miseg_conv3x3_stem_dgrad`` writes that
+    directly, so the layer returns no gradient for the padded operand and leaves the image's here."""
+    __slots__ = ("grad", "image")
+
+    def __init__(self):
+        self.grad = self.image = None
+
+    def take(self):
+        g, self.grad = self.grad, None
+        return g
+
+
+class _StemInput(torch.autograd.Function):
+    """``stem_input`` for an image that requires a gradient: the same operand (described or materialised), and a backward that returns
+    the image's fp32 gradient -- the stem kernel's (through the sink) or, on the generic path, the real channels of the padded
+    operand's gradient."""
+
+    @staticmethod
+    def forward(ctx, image: Tensor, dtype, sink: _StemSink):
+        ctx.set_materialize_grads(False)
+        ctx.sink, ctx.cin = sink, image.shape[1]
+        op = _stem_operand(image.detach(), dtype)
+        sink.image = getattr(op, "_miseg_stem_f32", None)
+        return op
+
+    @staticmethod
+    def backward(ctx, g: Optional[Tensor]):
+        gimage = ctx.sink.take()
+        if gimage is None and g is not None:
+            gimage = g[:, :ctx.cin].float().contiguous()
+        return gimage, None, None
+
+
 def stem_input(image: Tensor, dtype) -> Tensor:
-    """fp32 [B,Cin,H,W] image -> [B,VEC,H,W] channels_last tensor of ``dtype`` (extra channels zero)."""
+    """fp32 [B,Cin,H,W] image -> [B,VEC,H,W] channels_last tensor of ``dtype`` (extra channels zero).  An image that requires a
+    gradient gets it: through ``miseg_conv3x3_stem_dgrad`` for one channel, through the generic data-gradient path otherwise."""
+    if image.requires_grad and torch.is_grad_enabled():
+        sink = _StemSink()
+        out = _StemInput.apply(image, dtype, sink)
+        if sink.image is not None:             # the operand is only described (see _stem_operand): the description rides on the result
+            out._miseg_stem_f32 = sink.image
+        out._miseg_stem_sink = sink
+        return out
+    return _stem_operand(image, dtype)
+
+
+def _stem_operand(image: Tensor, dtype) -> Tensor:
     _need_gpu(image)
     pre = getattr(image, "_miseg_stem", None)      # the launch that assembled the batch wrote this operand too (ops.cat_flip)
     if pre is not None and pre[0] == dtype and pre[1].shape[0] == image.shape[0]:
@@ -308,6 +410,11 @@ class _ConvBNReLU(torch.autograd.Function):
                 running_var: Tensor, nbt: Tensor, training: bool, ups0: int, ups1: int, want_pool: bool, rec: Optional[_BnRec] = None,
                 rec0: Optional[_BnRec] = None, rec1: Optional[_BnRec] = None, sink: Optional[_GradSink] = None):
         _need_gpu(x0, x1, weight)
+        ctx.stem_sink = getattr(x0, "_miseg_stem_sink", None)      # stem_input's: the image itself wants a gradient
+        ctx.data_only = _data_grad_only
+        if training and _bn_untracked:       # frozen statistics: the kernels take null pointers as "do not track" (bn_untracked)
+            running_mean = running_var = nbt = None
+        use_acc = _BN_ACC and not _bn_float_stats      # (bn_float_statistics: the float partial sums for this forward)
         x0 = as_nhwc(x0)
         dtype, dev = x0.dtype, x0.device
         n, c0 = x0.shape[0], x0.shape[1]
@@ -330,9 +437,9 @@ class _ConvBNReLU(torch.autograd.Function):
         saved = torch.empty(4 * cout, dtype=torch.float32, device=dev)
         counter = SYNC_COUNTERS.take(dev) if training and query("miseg_conv3x3_bn_fwd_fusable", _DT[dtype], c0 + c1, n, h, w, cout) else None
         acc = None
-        if stem and training and (counter is not None or not _BN_ACC):
+        if stem and training and (counter is not None or not use_acc):
             stem, packed = False, _pack(weight, dtype, 0, cin=c0 + c1)       # (the stem kernel hands its statistics to the accumulator only)
-        if training and counter is None and _BN_ACC and (stem or query("miseg_conv3x3_fwd_acc_supported", _DT[dtype], c0 + c1, n, h, w, cout)):
+        if training and counter is None and use_acc and (stem or query("miseg_conv3x3_fwd_acc_supported", _DT[dtype], c0 + c1, n, h, w, cout)):
             # the statistics leave the convolution as fixed-point atomic adds into one [2 C] accumulator that the step block's upload
             # zeroed; the apply kernel turns them into coefficients itself: no partial rows, no finalize launch
             io = stepio.current()
@@ -412,13 +519,17 @@ class _ConvBNReLU(torch.autograd.Function):
                 gy[a:b] += g2.to(dtype)
         rec, rec0, rec1 = ctx.recs
         ext_parts, ext_nparts = rec.take(gy) if rec is not None else (None, 0)
-        if _FUSE_BN_BWD and not want_pool and gpool is None and gy is not None and _dgrads_fusable(ctx, dtype):
+        stem_dgrad = bool(ctx.needs_input_grad[0] and weight.shape[1] < c0)     # the gradient of the image behind a padded stem operand
+        if _FUSE_BN_BWD and not want_pool and gpool is None and gy is not None and not stem_dgrad and _dgrads_fusable(ctx, dtype):
             return _ConvBNReLU._backward_fused(ctx, gy, ext_parts, ext_nparts)
         gy = None if gy is None else as_nhwc(gy.to(dtype))
         gpool = None if gpool is None else as_nhwc(gpool.to(dtype))
         graw = empty_nhwc(n, cout, h, w, dtype, dev)
         pw, pg, pb = ctx.param_refs
-        ggamma, gbeta = grad_slot(pg), grad_slot(pb)   # written in place when the flat gradient buffer has an open slot
+        # written in place when the flat gradient buffer has an open slot -- only for a parameter whose gradient is wanted: a
+        # data-gradient-only pass (data_grad_only) neither claims nor writes a slot, its sums land in scratch and are dropped
+        want_g, want_b, want_w = (ctx.needs_input_grad[i] and not ctx.data_only for i in (3, 4, 2))
+        ggamma, gbeta = grad_slot(pg) if want_g else None, grad_slot(pb) if want_b else None
         if ggamma is None:
             ggamma = torch.empty(cout, dtype=torch.float32, device=dev)
         if gbeta is None:
@@ -450,11 +561,12 @@ class _ConvBNReLU(torch.autograd.Function):
                  int(training), _ptr(graw), _ptr(ggamma), _ptr(gbeta), _ptr(ws), ws.numel(), _ptr(SYNC_COUNTERS.take(dev)),
                  work=(0.0, float(raw.element_size()) * n * h * w * cout * 5.0), tag=f"bn_relu_bwd[{h}x{w},{cout}]")
         gw = None
-        if ctx.needs_input_grad[2]:
+        if want_w:
             gw = grad_slot(pw)
             side = None
             if gw is None:
                 gw = torch.empty_like(weight)
+                _second_user_waits(pw, dev)
             elif _WGRAD_SIDE and (_GRAPH_STREAMS or not torch.cuda.is_current_stream_capturing()):
                 side = wgrad_stream(dev)      # only when the result lands in the flat buffer: nothing on this stream touches it again
             cur = torch.cuda.current_stream(dev)
@@ -509,7 +621,18 @@ class _ConvBNReLU(torch.autograd.Function):
             call("miseg_conv3x3_dgrad_dual", _stream(), _DT[dtype], _ptr(graw), cout, n, h, w, _ptr(packed), c0, _ptr(g0), c1, _ptr(g1),
                  work=(18.0 * (c0 + c1) * cout * n * h * w, float(raw.element_size()) * n * h * w * (c0 + c1 + cout)),
                  tag=f"conv3x3_dgrad[{h}x{w},{cout}->{c0}+{c1}]")
-            return g0, g1, gw, ggamma, gbeta, None, None, None, None, None, None, None, None, None, None, None
+            return g0, g1, gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
+        if stem_dgrad:
+            cin = weight.shape[1]
+            sink = ctx.stem_sink
+            if sink is not None and _STEM_DGRAD and cin == 1 and query("miseg_conv3x3_stem_dgrad_supported", _DT[dtype], cout, w):
+                # one image channel: the stem's own kernel writes the fp32 image gradient; it reaches the image through the sink
+                from .ops import stem_dgrad as _stem_dgrad
+                sink.grad = _stem_dgrad(graw, weight)
+                return None, None, gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
+            # the generic path; the padded channels' gradients are computed and dropped (stem_input's backward keeps the real ones)
+            gfull = stem_dgrad_generic(graw, weight, c0)
+            return gfull, None, gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
         for s, (cb, cs, ups, xs) in enumerate(((0, c0, ups0, x0), (c0, c1, ups1, x1))):
             if xs is None or not ctx.needs_input_grad[s]:
                 continue
@@ -559,7 +682,7 @@ class _ConvBNReLU(torch.autograd.Function):
                 call("miseg_sumpool2x2", _stream(), _DT[dtype], _ptr(gfull), n, h, w, cs, _ptr(glow), 0)
                 gfull = glow
             grads[s] = gfull
-        return grads[0], grads[1], gw, ggamma, gbeta, None, None, None, None, None, None, None, None, None, None, None
+        return grads[0], grads[1], gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
 
     @staticmethod
     def _backward_fused(ctx, gy_in: Tensor, ext_parts: Optional[Tensor], ext_nparts: int):
@@ -569,7 +692,8 @@ class _ConvBNReLU(torch.autograd.Function):
         dtype, dev, es = raw.dtype, raw.device, raw.element_size()
         gy = as_nhwc(gy_in.to(dtype))
         pw, pg, pb = ctx.param_refs
-        ggamma, gbeta = grad_slot(pg), grad_slot(pb)
+        want_g, want_b, want_w = (ctx.needs_input_grad[i] and not ctx.data_only for i in (3, 4, 2))     # (see backward)
+        ggamma, gbeta = grad_slot(pg) if want_g else None, grad_slot(pb) if want_b else None
         if ggamma is None:
             ggamma = torch.empty(cout, dtype=torch.float32, device=dev)
         if gbeta is None:
@@ -584,11 +708,12 @@ class _ConvBNReLU(torch.autograd.Function):
                  _ptr(coef), _ptr(ggamma), _ptr(gbeta), None, 0, _ptr(ws), ws.numel(),
                  work=(0.0, float(es) * n * h * w * cout * 2.0), tag=f"bn_relu_bwd[{h}x{w},{cout}]")
         gw = None
-        if ctx.needs_input_grad[2]:
+        if want_w:
             gw = grad_slot(pw)
             side = None
             if gw is None:
                 gw = torch.empty_like(weight)
+                _second_user_waits(pw, dev)
             elif _WGRAD_SIDE and (_GRAPH_STREAMS or not torch.cuda.is_current_stream_capturing()):
                 side = wgrad_stream(dev)
             cur = torch.cuda.current_stream(dev)
@@ -633,7 +758,31 @@ class _ConvBNReLU(torch.autograd.Function):
                 call("miseg_sumpool2x2", _stream(), _DT[dtype], _ptr(gfull), n, h, w, cs, _ptr(glow), 0)
                 gfull = glow
             grads[s] = gfull
-        return grads[0], grads[1], gw, ggamma, gbeta, None, None, None, None, None, None, None, None, None, None, None
+        return grads[0], grads[1], gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
+
+
+def stem_dgrad_generic(graw: Tensor, weight: Tensor, cp: int) -> Tensor:
+    """The stem's data gradient without its own kernel: ``weight`` (fp32 [Cout,Cin,3,3], Cin below one channel vector) with its input
+    channels zero-padded to ``cp``, packed for the data gradient (kind 1), through the streaming / tiled convolution over ``graw``
+    (NHWC [N,Cout,H,W] of the storage type) -> the gradient of the padded operand, NHWC [N,cp,H,W] of the storage type: channels
+    [0, Cin) are the image's, the rest are zero.  Any width, any channel count the convolutions take."""
+    n, cout, h, w = graw.shape
+    cin = weight.shape[1]
+    wpad = torch.zeros((cout, cp, 3, 3), dtype=torch.float32, device=graw.device)
+    wpad[:, :cin] = weight
+    gfull = empty_nhwc(n, cp, h, w, graw.dtype, graw.device)
+    call("miseg_conv3x3_fwd", _stream(), _DT[graw.dtype], _ptr(graw), cout, 0, None, 0, 0, n, h, w, _ptr(_pack_now(wpad, graw.dtype, 1, 0, cp)), cp,
+         _ptr(gfull), None, work=(18.0 * cp * cout * n * h * w, float(graw.element_size()) * n * h * w * (cp + cout)),
+         tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cp}]")
+    return gfull
+
+
+def _second_user_waits(pw, dev) -> None:
+    """A weight used by two forward passes of one backward (VAT: the labeled and the perturbed pass): the first user's weight gradient
+    went into the flat slot from the side stream, this user's goes into a tensor of its own and autograd ADDS it into that slot on the
+    current stream -- which therefore has to see the side stream's launch first."""
+    if getattr(pw, "_miseg_grad_slot", None) is not None and dev in _wgrad_dirty:
+        wait_stream(torch.cuda.current_stream(dev), wgrad_stream(dev))
 
 
 def _dgrads_fusable(ctx, dtype) -> bool:
@@ -690,6 +839,7 @@ class _Conv1x1(torch.autograd.Function):
         ctx.save_for_backward(x, wf)
         ctx.wshape = tuple(weight.shape)
         ctx.param_refs = (weight, bias)
+        ctx.data_only = _data_grad_only
         return out
 
     @staticmethod
@@ -700,7 +850,9 @@ class _Conv1x1(torch.autograd.Function):
         gout = as_nhwc(gout.float())
         gin = empty_nhwc(n, cin, h, w, x.dtype, x.device) if ctx.needs_input_grad[0] else None
         pw, pb = ctx.param_refs
-        gw, gb = grad_slot(pw), grad_slot(pb)       # written in place when the flat gradient buffer has an open slot
+        want_w, want_b = (ctx.needs_input_grad[i] and not ctx.data_only for i in (1, 2))     # (a data_grad_only pass: scratch, dropped)
+        # written in place when the flat gradient buffer has an open slot
+        gw, gb = grad_slot(pw) if want_w else None, grad_slot(pb) if want_b else None
         gw = gw.view(cout, cin) if gw is not None else torch.empty_like(wf)
         if gb is None:
             gb = torch.empty(cout, dtype=torch.float32, device=x.device)
@@ -710,7 +862,7 @@ class _Conv1x1(torch.autograd.Function):
         if gin is not None:
             from .ops import _GradJoin
             _GradJoin.offer(x, gin)      # a tap's head backward may add its gradient of x into this tensor (ops._GradJoin)
-        return gin, gw.view(ctx.wshape), gb
+        return gin, gw.view(ctx.wshape) if want_w else None, gb if want_b else None
 
 
 def conv1x1(x: Tensor, weight: Tensor, bias: Tensor) -> Tensor:

@@ -1007,6 +1007,67 @@ class EntropyMinEpocher(TrainEpocher):
             self.meters["entropy"].add(host["entropy"])
 
 
+class VATEpocher(TrainEpocher):
+    """``vat``: virtual adversarial training (``VATParameters``).  One iteration:
+
+        sup   = KL(softmax(f(x_l)), onehot(y_l))          the labeled batch alone, as its own BatchNorm batch
+        reg   = VATLoss(xi, eps, prop_eps, ip)(f, x_u)    deepclustering2.utils.VAT: clean pass, ``ip`` direction passes, perturbed pass
+        total = sup + reg_weight * reg                    one backward, Adam
+
+    ``3 + ip`` U-Net forwards per iteration: the labeled and the clean unlabeled pass move the BatchNorm running statistics (in that
+    order), the direction and perturbed passes use batch statistics and leave them alone.  The passes of the loss take their batch
+    statistics from float partial sums (``unet_ops.bn_float_statistics``), the labeled pass from the step block's accumulators.  The direction passes' backward computes
+    data gradients only -- down to the image, through ``miseg_conv3x3_stem_dgrad`` -- and touches no ``param.grad``; the weights are
+    used twice by the parameter backward (labeled and perturbed pass) and autograd adds the second gradient to the flat slot the
+    first one wrote.  The unlabeled loader's flip decisions are drawn as in ``partial`` (the host random streams stay aligned) and not
+    applied.  The random direction is the library generator's, seeded with the iteration's seed.  A direction of zero / non-finite
+    norm raises a deferred check: the guarded Adam skips that update and the host raises one iteration later.
+
+    The iteration runs eagerly: ``enable_step_tape`` is a no-op here.  A replayed launch tape repeats the recorded arguments, and
+    ``miseg_normal_fill`` takes its seed by value: every replay would draw the recorded iteration's direction.  (The direction pass
+    also scales the distance's gradient with one torch product, which the recording would refuse.)  Meters: the base ones plus
+    ``reg_weight``."""
+
+    _TAPE_DEFAULT = False
+
+    def __init__(self, model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_weight: float, num_batches: int,
+                 cur_epoch: int = 0, device="cpu", feature_position=None, feature_importance=None, xi: float = 10.0, eps: float = 1.0,
+                 prop_eps: float = 0.25, ip: int = 1) -> None:
+        super().__init__(model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_weight, num_batches, cur_epoch,
+                         device, feature_position, feature_importance)
+        from deepclustering2.utils.VAT import VATLoss
+        self._vat = VATLoss(xi=xi, eps=eps, prop_eps=prop_eps, ip=ip)
+
+    def enable_step_tape(self, warmup: int = 3) -> None:
+        """No-op: the ``vat`` iteration runs eagerly (class docstring)."""
+
+    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
+        meters = super()._configure_meters(meters)
+        meters.register_meter("reg_weight", AverageValueMeter())
+        return meters
+
+    def _run(self, *args, **kwargs) -> EpochResultDict:
+        self.meters["reg_weight"].add(self._reg_weight)
+        return super()._run(*args, **kwargs)
+
+    def _device_step(self, labeled_image: Tensor, labeled_target: Tensor, unlabeled_image: Tensor, flips2: Tensor, seed: int = None):
+        seed = self._seed if seed is None else seed
+        self._flips2 = flips2
+        labels = labeled_target.squeeze(1)
+        with checks.deferred(self._pending.checks):
+            self._before_forward(len(unlabeled_image))
+            try:
+                label_logits = self._model(labeled_image)
+            finally:
+                self._after_forward()
+            if isinstance(self._sup_criterion, KL_div) and self._sup_criterion.supports_fused():
+                sup_loss = self._sup_criterion.from_logits(label_logits, labels)
+            else:
+                sup_loss = self._sup_criterion(label_logits.softmax(1), class2one_hot(labels, self.num_classes))
+            lds, _, _ = self._vat(self._model, unlabeled_image, seed=seed)
+        return self._finish_step(LinearLoss.of(sup_loss), LinearLoss.of(lds), label_logits, labels)
+
+
 class PretrainEncoderEpocher(_Epocher):
     """``contrast``: contrastive pre-training of the encoder (ref contrastyou/epocher/contrast_epocher.py:21-113, DESIGN.md section
     14).  One iteration: unpack the two augmented views, ONE train-mode forward of ``cat([img, img_tf])`` up to ``extract_position``

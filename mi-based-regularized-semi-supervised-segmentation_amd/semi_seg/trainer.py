@@ -1,7 +1,8 @@
 """The semi-supervised trainers behind ``Trainer.name`` (ref ``semi_seg/trainer.py:24-214``).
 
 Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT, and ``midl`` and
-``entmin``, the ``MIDLPaperParameters`` and ``EntropyMinParameters`` sections' trainers, and ``contrast`` and ``contrastdecoder``, the
+``entmin``, the ``MIDLPaperParameters`` and ``EntropyMinParameters`` sections' trainers, ``vat``, virtual adversarial training on the
+wheel's ``VATLoss``, and ``contrast`` and ``contrastdecoder``, the
 encoder and decoder stages of the reference's contrastive pre-training), the keyword-only constructor, ``init()``,
 ``start_training()``, ``inference(checkpoint)``, ``set_feature_positions`` and the attribute names the checkpoint tree is
 keyed by (``_model``, ``_optimizer``, ``_scheduler``, ``_projector_wrappers``, ``_IIDSegWrapper``, ``_storage`` ...; the
@@ -309,6 +310,46 @@ class EntropyMinTrainer(SemiTrainer):
                                    reg_weight=self._reg_weight, **self._epoch_args())
 
 
+class VATTrainer(SemiTrainer):
+    """``vat``: + ``VATParameters.weight`` x the virtual adversarial loss of the unlabeled batch (``deepclustering2.utils.VAT.VATLoss``
+    with ``xi``, ``eps``, ``prop_eps``, ``ip``: a clean pass, ``ip`` direction passes that end in the gradient with respect to the image,
+    one perturbed pass).  The section is optional: missing keys take the class's defaults and ``weight`` 1.  No new modules -- the
+    criterion is built inside the epocher --, so the checkpoint tree is the ``partial`` trainer's, and validation, test and
+    ``inference`` are ``partial``'s.  ``Arch.compute_dtype=float16`` is refused (no loss scaling in the direction pass), and so are
+    data-parallel runs.  Semantics: DESIGN.md section 23."""
+
+    DEFAULTS = dict(weight=1.0, xi=10.0, eps=1.0, prop_eps=0.25, ip=1)
+
+    @classmethod
+    def parameters(cls, configuration) -> dict:
+        """``VATParameters`` of a configuration over the defaults; unknown keys are an error."""
+        section = dict((configuration or {}).get("VATParameters") or {})
+        unknown = sorted(set(section) - set(cls.DEFAULTS))
+        if unknown:
+            raise KeyError(f"VATParameters: unknown keys {unknown}; known: {sorted(cls.DEFAULTS)}")
+        merged = {**cls.DEFAULTS, **section}
+        return dict(weight=float(merged["weight"]), xi=float(merged["xi"]), eps=float(merged["eps"]), prop_eps=float(merged["prop_eps"]),
+                    ip=int(merged["ip"]))
+
+    def _init(self) -> None:
+        super()._init()
+        if getattr(self._model, "compute_dtype", torch.float32) == torch.float16:
+            raise NotImplementedError("Trainer.name=vat has no loss scaling in its direction pass: use Arch.compute_dtype float32 or bfloat16")
+        params = self.parameters(self._config)
+        self._reg_weight = params.pop("weight")
+        self._vat_params = params
+
+    def attach_data_parallel(self, num_buckets: int = 3):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise RuntimeError("Trainer.name=vat runs in a single process: the gradient reducer's hooks would also fire in the direction pass")
+        return None
+
+    def _make_epocher(self):
+        return E.VATEpocher(self._model, self._optimizer, self._labeled_loader, self._unlabeled_loader, self._sup_criterion,
+                            reg_weight=self._reg_weight, **self._vat_params, **self._epoch_args())
+
+
 class ContrastTrainer(SemiTrainer):
     """``contrast``: contrastive pre-training of the encoder (the encoder stage of ref contrastyou/trainer/contrast_trainer.py:64-114;
     DESIGN.md section 14).  ``unlabeled_loader`` is the pre-training loader; the labeled, validation and test loaders are accepted and
@@ -458,5 +499,5 @@ class ContrastDecoderTrainer(ContrastTrainer):
 
 
 trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer, "meanteacher": MeanTeacherTrainer,
-                "midl": MIDLTrainer, "entmin": EntropyMinTrainer, "contrast": ContrastTrainer,
+                "midl": MIDLTrainer, "entmin": EntropyMinTrainer, "vat": VATTrainer, "contrast": ContrastTrainer,
                 "contrastdecoder": ContrastDecoderTrainer}
