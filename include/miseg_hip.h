@@ -666,6 +666,23 @@ int miseg_adam_step_scaled(void* stream, float* param, const float* grad, float*
 int miseg_adam_step_guarded(void* stream, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                             int64_t numel, float beta1, float beta2, const float* hyper, float grad_scale,
                             const float* guard, int64_t nguard);
+/* RAdam as the wheel states it (whl:deepclustering2/optim/radam.py:16-91; not torch.optim.RAdam's rule), elementwise over the same
+ * flat fp32 buffers:   v = v*b2 + (1-b2)*g*g;  m = m*b1 + (1-b1)*g;  p += -(wd*lr)*p;
+ *                      rectified ? p += -step_size*m / (sqrt(v) + eps) : p += -step_size*m          (g = grad / grad_scale, no L2 term)
+ * hyper = device fp32[5]: step_size, rectified (N_sma >= 5) as 1 / 0, eps, wd*lr, 1 / loss scale -- everything a step changes is
+ * computed on the host in double and read from device memory, since a replayed launch tape replays by-value arguments and the rule
+ * turns rectified at its sixth step.  beta1 / beta2 are doubles: 1 - beta is rounded to fp32 from double, as torch rounds it.
+ * grad_scale, guard, nguard: as miseg_adam_step_guarded (a set or NaN flag leaves p, m and v untouched). */
+int miseg_radam_step(void* stream, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
+                     double beta1, double beta2, const float* hyper, float grad_scale, const float* guard, int64_t nguard);
+/* AdaBound (decoupled = 0) and AdaBoundW (decoupled = 1), whl:deepclustering2/optim/adabound.py:67-136,199-270:
+ *   decoupled ? g : g += wd*p;  m, v as above;  max_exp_avg_sq ? vmax = max(vmax, v) (amsbound; may be null) : -;
+ *   p -= clamp(step_size / (sqrt(vmax or v) + eps), lower, upper) * m;  decoupled: then p -= wd * (p before the step).
+ * hyper = device fp32[6]: step_size = lr*sqrt(bc2)/bc1, lower, eps, wd, 1 / loss scale, upper (the bounds follow the step count and,
+ * through final_lr * lr / base_lr, the scheduler).  A set or NaN guard flag leaves p, m, v and vmax untouched. */
+int miseg_adabound_step(void* stream, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                        int64_t numel, double beta1, double beta2, const float* hyper, int decoupled, float grad_scale,
+                        const float* guard, int64_t nguard);
 /* Mean Teacher EMA on flat fp32 buffers laid out alike   ref: whl:deepclustering2/models/ema.py:107-131
  * teacher[i] = (teacher[i] * coef[0] + coef[1] * student[i]) * coef[2], coef = device fp32[3] (alpha, 1 - alpha, 1 - weight_decay) --
  * the iteration's step block, so a replayed launch tape reads each step's alpha.  Rounded as torch's eager

@@ -203,7 +203,7 @@ def attach(trainer, num_buckets: int = 3) -> Optional[GradReducer]:
         return None
     optimizer = trainer._optimizer
     if not hasattr(optimizer, "flat"):
-        raise RuntimeError("data-parallel training needs the flat-buffer FusedAdam (Optim.name: Adam)")
+        raise RuntimeError("data-parallel training needs a flat-buffer fused optimiser (Optim.name: Adam, RAdam, AdaBound or AdaBoundW)")
     trainer.to(trainer._device)
     trainer._grad_reducer = GradReducer(optimizer.flat, num_buckets=num_buckets)
     teacher, updater = getattr(trainer, "_teacher_model", None), getattr(trainer, "_ema_updater", None)

@@ -22,7 +22,9 @@ from . import _cabi
 from ._cabi import call
 
 FLIPS_OFF, FLIPS_CAP = 0, 512                 # int32
-HYPER_OFF, HYPER_CAP = 2048, 64               # float32: 8 per parameter group (lr/bc1, 1/sqrt(bc2), eps, wd, 1/loss scale)
+HYPER_OFF, HYPER_CAP = 2048, 64               # float32: 8 per parameter group (Adam: lr/bc1, 1/sqrt(bc2), eps, wd, 1/loss scale; words
+#                                               5-7: what a longer row brings -- AdaBound's upper bound; flat.FusedAdam.host_step)
+HYPER_ROW = 7                                 # values an optimiser's row may carry: words 0-3, then 5-7 (word 4 stays 1 / loss scale)
 COUNT_OFF, COUNT_CAP = 2304, 64               # int32, zero on the host: the upload zeroes the counters
 import os as _os
 # (the opt-in accumulators of the BatchNorm backward need 6 892 more words)
@@ -113,8 +115,12 @@ class StepIO:
             hi[FLIPS_OFF // 4:FLIPS_OFF // 4 + n] = torch.as_tensor(list(flip_masks), dtype=torch.int32)
         self._n_flips, self._groups, self.scale = n, len(hyper_rows), float(scale)
         for gi, row in enumerate(hyper_rows):
-            vals = list(row)[:4] + [1.0 / float(scale)]
-            hf[HYPER_OFF // 4 + 8 * gi:HYPER_OFF // 4 + 8 * gi + 5] = torch.tensor(vals, dtype=torch.float32)
+            row = list(row)
+            if len(row) > HYPER_ROW:
+                raise _cabi.MisegError(f"StepIO: a row of {len(row)} scalars exceeds the block layout's {HYPER_ROW}")
+            row += [0.0] * (HYPER_ROW - len(row))
+            vals = row[:4] + [1.0 / float(scale)] + row[4:]
+            hf[HYPER_OFF // 4 + 8 * gi:HYPER_OFF // 4 + 8 * gi + 8] = torch.tensor(vals, dtype=torch.float32)
         for (numel, coeff), (off, _) in self._seeds.items():
             hf[SEED_OFF // 4 + off:SEED_OFF // 4 + off + numel] = coeff * float(scale)
         self._cursor_counter = self._cursor_arena = self._cursor_out = self._cursor_acc = 0
@@ -138,7 +144,8 @@ class StepIO:
         return self._d_i32[FLIPS_OFF // 4:FLIPS_OFF // 4 + n]
 
     def hyper(self, gi: int) -> Tensor:
-        return self._d_f32[HYPER_OFF // 4 + 8 * gi:HYPER_OFF // 4 + 8 * gi + 5]
+        """Group ``gi``'s eight device words: the row's values 0-3, 1 / loss scale, the row's values 4-6."""
+        return self._d_f32[HYPER_OFF // 4 + 8 * gi:HYPER_OFF // 4 + 8 * gi + 8]
 
     def counter(self) -> Tensor:
         """A 0-d int32 device counter that is zero at the start of the iteration (the upload wrote it)."""

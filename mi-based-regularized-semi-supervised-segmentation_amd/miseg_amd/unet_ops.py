@@ -893,6 +893,37 @@ def adam_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, 
          float(beta2), _ptr(hyper), float(grad_scale), _ptr(guard), 0 if guard is None else guard.numel())
 
 
+def _flat_step_args(param: Tensor, grad: Tensor, states, hyper: Tensor, words: int, guard: Optional[Tensor]) -> None:
+    _need_gpu(param, grad, hyper, *states)
+    for t in (grad, *states):
+        assert t.dtype == param.dtype == torch.float32 and t.numel() == param.numel() and t.is_contiguous() and param.is_contiguous()
+    assert hyper.dtype == torch.float32 and hyper.is_contiguous() and hyper.numel() >= words
+    if guard is not None:
+        _need_gpu(guard)
+        assert guard.dtype == torch.float32 and guard.is_contiguous()
+
+
+def radam_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, hyper: Tensor, beta1: float, beta2: float,
+               grad_scale: float = 1.0, guard: Optional[Tensor] = None) -> None:
+    """The wheel's RAdam on flat fp32 buffers (``miseg_radam_step``); ``hyper`` = device fp32[5] (step size, rectified as 1 / 0, eps,
+    weight decay x lr, 1 / loss scale); ``grad_scale`` and ``guard`` as ``adam_step``'s (-1: the kernel reads ``hyper[4]``)."""
+    _flat_step_args(param, grad, (exp_avg, exp_avg_sq), hyper, 5, guard)
+    call("miseg_radam_step", _stream(), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), float(beta1),
+         float(beta2), _ptr(hyper), float(grad_scale), _ptr(guard), 0 if guard is None else guard.numel())
+
+
+def adabound_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, max_exp_avg_sq: Optional[Tensor], hyper: Tensor,
+                  beta1: float, beta2: float, decoupled: bool, grad_scale: float = 1.0, guard: Optional[Tensor] = None) -> None:
+    """The wheel's AdaBound (``decoupled`` weight decay: AdaBoundW) on flat fp32 buffers (``miseg_adabound_step``); ``hyper`` = device
+    fp32[6] (step size, lower bound, eps, weight decay, 1 / loss scale, upper bound); ``max_exp_avg_sq``: the amsbound variant's
+    running maximum, or None."""
+    states = (exp_avg, exp_avg_sq) if max_exp_avg_sq is None else (exp_avg, exp_avg_sq, max_exp_avg_sq)
+    _flat_step_args(param, grad, states, hyper, 6, guard)
+    call("miseg_adabound_step", _stream(), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(max_exp_avg_sq), param.numel(),
+         float(beta1), float(beta2), _ptr(hyper), int(bool(decoupled)), float(grad_scale), _ptr(guard),
+         0 if guard is None else guard.numel())
+
+
 def ema_update(teacher: Tensor, student: Tensor, coef: Tensor, guard: Optional[Tensor] = None) -> None:
     """Mean Teacher EMA on flat fp32 buffers laid out alike: ``teacher = (teacher * a + b * student) * d`` with ``coef`` = device
     fp32[3] (a, b, d) = (alpha, 1 - alpha, 1 - weight_decay), rounded as torch's eager ``mul_ / add_ / mul_`` (include/miseg_hip.h);

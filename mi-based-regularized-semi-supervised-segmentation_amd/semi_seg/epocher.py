@@ -402,7 +402,7 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         # BatchNorm buffers would leave the recorded pointers dangling -- a changed address re-records instead
         opt = self._optimizer
         where = tuple((fb.flat_param.data_ptr(), fb.flat_grad.data_ptr()) for fb in getattr(opt, "_flats", []) if fb.flat_param is not None)
-        where += tuple(t.data_ptr() for t in getattr(opt, "_m", []) if t is not None)
+        where += tuple(t.data_ptr() for name in ("_m", "_vmax") for t in getattr(opt, name, []) if t is not None)
         buf = next(iter(self._model.buffers()), None)
         return (type(self).__name__, float(self._reg_weight), getattr(self, "_cons_weight", None), getattr(self, "_iic_weight", None),
                 tuple(self._feature_importance), tuple(self._feature_position), type(self._sup_criterion).__name__,
@@ -414,7 +414,8 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         if scale == 1.0:
             return 1.0
         if not hasattr(self._optimizer, "grad_scale"):
-            raise RuntimeError("Arch.compute_dtype=float16 needs the fused Adam (Optim.name=Adam), which undoes the loss scale")
+            raise RuntimeError("Arch.compute_dtype=float16 needs a fused optimiser (Optim.name=Adam, RAdam, AdaBound or AdaBoundW), "
+                               "which undoes the loss scale")
         if self._optimizer.loss_scaler is None:
             from miseg_amd.flat import LossScaler
             self._optimizer.loss_scaler = LossScaler(scale)
@@ -845,9 +846,9 @@ class MeanTeacherEpocher(TrainEpocher):
         return super()._run(*args, **kwargs)
 
     def _stage(self, io, flip_masks) -> int:
-        """Adam's rows, then the EMA's (alpha, 1 - alpha, 1 - weight decay) of this call as one more row of the block."""
+        """The fused optimiser's rows, then the EMA's (alpha, 1 - alpha, 1 - weight decay) of this call as one more row of the block."""
         if not hasattr(self._optimizer, "host_step"):
-            raise RuntimeError("Trainer.name=meanteacher needs the fused Adam (Optim.name: Adam)")
+            raise RuntimeError("Trainer.name=meanteacher needs a fused optimiser (Optim.name: Adam, RAdam, AdaBound or AdaBoundW)")
         rows = self._optimizer.host_step()
         scale = self._loss_scale()
         self._optimizer.grad_scale = scale
