@@ -91,7 +91,7 @@ class _Pending:
         return scalars[len(names):] if items else None
 
     def take_static(self):
-        """(names, device vector, check items) of ``precompute`` / ``set_static``, removed."""
+        """(names, device vector, check items) of ``precompute``, removed."""
         st, self._static = self._static, None
         return st
 
@@ -172,14 +172,25 @@ class _Pending:
         checks.raise_failed(items, vals[len(names):])
         return out, extras
 
-    def drain(self):
-        """(names, device scalars, check items) recorded so far, cleared -- used while capturing a step graph."""
-        names, vals, items = self._names, self._vals, list(self.checks)
-        self._names, self._vals, self.checks[:] = [], [], []
-        return names, vals, items
 
-    def set_static(self, names, scalars: Tensor, items) -> None:
-        self._static = (names, scalars, items)
+def supervised_loss(criterion: T_loss, logits: Tensor, labels: Tensor, num_classes: int, disable_assert: bool = False) -> Tensor:
+    """``criterion(softmax(logits), one_hot(labels))`` (ref :165-166): one fused kernel where the criterion has it, else the
+    reference's call on materialised operands.  ``disable_assert`` is the evaluation's (no autograd there for ``KL_div`` to insist on)."""
+    if isinstance(criterion, KL_div) and criterion.supports_fused():
+        return criterion.from_logits(logits, labels)
+    flags = {"disable_assert": True} if disable_assert else {}
+    return criterion(logits.softmax(1), class2one_hot(labels, num_classes), **flags)
+
+
+def consistency_loss(criterion: T_loss, student_tf_logits: Tensor, other_logits: Tensor, flips: Tensor):
+    """``criterion(softmax(student(flip(u))), softmax(flip(other(u))).detach())`` (ref :221-224): flip, both softmaxes and the
+    distance are one fused kernel for ``nn.MSELoss`` and the fused ``KL_div`` (``name: mse | kl``)."""
+    if isinstance(criterion, nn.MSELoss):
+        return LinearLoss.of(ops.softmax_mse(student_tf_logits, other_logits, flips))
+    if isinstance(criterion, KL_div) and criterion.supports_fused():
+        return LinearLoss.of(ops.softmax_kl_consistency(student_tf_logits, other_logits, flips))
+    # any other criterion object: called as the reference calls it, on materialised operands
+    return criterion(student_tf_logits.softmax(1), ops.flip(other_logits, flips).softmax(1).detach())
 
 
 class EvalEpocher(_num_class_mixin, _Epocher):
@@ -197,24 +208,27 @@ class EvalEpocher(_num_class_mixin, _Epocher):
         meters.register_meter("dice", UniversalDice(self.num_classes, report_axises=list(range(1, self.num_classes))))
         return meters
 
+    _WANT_PRED = False        # whether ``_after_batch`` needs the class map (it gets None without)
+
     @torch.no_grad()
     def _run(self, *args, **kwargs) -> Tuple[EpochResultDict, float]:
         self._model.eval()
         report_dict = EpochResultDict()
         for _, val_data in zip(self._indicator, self._val_loader):
-            val_img, val_target, _file_path, _, group = self._unzip_data(val_data, self._device)
+            val_img, val_target, file_path, _, group = self._unzip_data(val_data, self._device)
             val_logits = self._model(val_img)
             labels = val_target.squeeze(1)
-            if isinstance(self._sup_criterion, KL_div) and self._sup_criterion.supports_fused():
-                val_loss = self._sup_criterion.from_logits(val_logits, labels)
-            else:
-                val_loss = self._sup_criterion(val_logits.softmax(1), class2one_hot(labels, self.num_classes), disable_assert=True)
-            _, inter, union = ops.argmax_dice(val_logits, labels, want_pred=False)
+            val_loss = supervised_loss(self._sup_criterion, val_logits, labels, self.num_classes, disable_assert=True)
+            pred, inter, union = ops.argmax_dice(val_logits, labels, want_pred=self._WANT_PRED)
             self.meters["loss"].add(val_loss.item())
             self.meters["dice"].add_counts(inter, union, group_name=group)
+            self._after_batch(val_img, val_target, val_logits, pred, file_path, group)
             report_dict = self.meters.tracking_status()
             self._indicator.set_postfix_dict(report_dict)
         return report_dict, self.meters["dice"].summary()["DSC_mean"]
+
+    def _after_batch(self, val_img, val_target, val_logits, pred, file_path, group) -> None:   # what an evaluation adds per batch
+        pass
 
     @staticmethod
     def _unzip_data(data, device):
@@ -268,34 +282,20 @@ class InferenceEpocher(EvalEpocher):
             except RuntimeError:
                 pass
 
-    @torch.no_grad()
-    def _run(self, *args, **kwargs) -> Tuple[EpochResultDict, float]:
-        self._model.eval()
-        report_dict = EpochResultDict()
-        for _, val_data in zip(self._indicator, self._val_loader):
-            val_img, val_target, file_path, _, group = self._unzip_data(val_data, self._device)
-            val_logits = self._model(val_img)
-            write_img_target(val_img, val_target, self._save_dir, file_path)
-            write_predict(val_logits, self._save_dir, file_path)
-            labels = val_target.squeeze(1)
-            if isinstance(self._sup_criterion, KL_div) and self._sup_criterion.supports_fused():
-                val_loss = self._sup_criterion.from_logits(val_logits, labels)
-            else:
-                val_loss = self._sup_criterion(val_logits.softmax(1), class2one_hot(labels, self.num_classes), disable_assert=True)
-            pred, inter, union = ops.argmax_dice(val_logits, labels, want_pred=True)
-            self.meters["loss"].add(val_loss.item())
-            self.meters["dice"].add_counts(inter, union, group_name=group)
-            self._add_surface(pred, labels)
-            if self._keep_largest:
-                cleaned, _, (inter_lcc, union_lcc) = ops.largest_component(
-                    pred, list(range(1, self.num_classes)), volume=False, connectivity=self._component_connectivity, fill=0,
-                    target=labels.contiguous().long(), num_classes=self.num_classes)
-                self.meters["dice_lcc"].add_counts(inter_lcc, union_lcc, group_name=group)
-                self._add_surface(cleaned, labels, "_lcc")
-                write_prediction_map(cleaned, self._save_dir, file_path, "pred_lcc")
-            report_dict = self.meters.tracking_status()
-            self._indicator.set_postfix_dict(report_dict)
-        return report_dict, self.meters["dice"].summary()["DSC_mean"]
+    _WANT_PRED = True
+
+    def _after_batch(self, val_img, val_target, val_logits, pred, file_path, group) -> None:
+        write_img_target(val_img, val_target, self._save_dir, file_path)
+        write_predict(val_logits, self._save_dir, file_path)
+        labels = val_target.squeeze(1)
+        self._add_surface(pred, labels)
+        if self._keep_largest:
+            cleaned, _, (inter_lcc, union_lcc) = ops.largest_component(
+                pred, list(range(1, self.num_classes)), volume=False, connectivity=self._component_connectivity, fill=0,
+                target=labels.contiguous().long(), num_classes=self.num_classes)
+            self.meters["dice_lcc"].add_counts(inter_lcc, union_lcc, group_name=group)
+            self._add_surface(cleaned, labels, "_lcc")
+            write_prediction_map(cleaned, self._save_dir, file_path, "pred_lcc")
 
 
 class TrainEpocher(_num_class_mixin, _Epocher):
@@ -315,11 +315,19 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         self._feature_position, self._feature_importance = feature_position, feature_importance
         self._reducer = None  # set by miseg_amd.ddp.attach() for data-parallel runs
 
+    # The meters a class ADDS, in the order of the report's columns.  ``_configure_meters`` registers those of the whole class chain,
+    # base first; ``_record`` feeds each one whose name is a key of the iteration's host dict.  What is not a host value (the Dice
+    # counts, ``lr``, the weights, the per-tap ``individual_mis``) is fed where it is known.
+    METERS: Tuple[str, ...] = ("lr", "sup_loss", "reg_loss", "sup_dice")
+
     def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
-        meters.register_meter("lr", AverageValueMeter())
-        meters.register_meter("sup_loss", AverageValueMeter())
-        meters.register_meter("reg_loss", AverageValueMeter())
-        meters.register_meter("sup_dice", UniversalDice(self.num_classes, report_axises=list(range(1, self.num_classes))))
+        for klass in reversed(type(self).__mro__):
+            for name in vars(klass).get("METERS", ()):
+                if name == "sup_dice":
+                    meter = UniversalDice(self.num_classes, report_axises=list(range(1, self.num_classes)))
+                else:
+                    meter = MultipleAverageValueMeter() if name == "individual_mis" else AverageValueMeter()
+                meters.register_meter(name, meter)
         return meters
 
     # ---- one optimisation step
@@ -463,6 +471,29 @@ class TrainEpocher(_num_class_mixin, _Epocher):
     def _after_forward(self) -> None:
         pass
 
+    def _forward(self, batch: Tensor, ub: int) -> Tensor:
+        """One training forward of the network, between the forward hooks; its simplex / NaN assertions are deferred to this
+        iteration's fetch()."""
+        with checks.deferred(self._pending.checks):
+            self._before_forward(ub)
+            try:
+                return self._model(batch)
+            finally:
+                self._after_forward()
+
+    def _assemble(self, labeled_image: Tensor, unlabeled_image: Tensor, flips: Tensor, keep_unflipped: bool) -> Tensor:
+        """The network's batch, ``[labeled | unlabeled | flip(unlabeled)]`` or, without ``keep_unflipped``, ``[labeled |
+        flip(unlabeled)]`` (ref :148-153: per-sample flips, stack, cat): one launch where the kernels take the operands."""
+        if labeled_image.dtype == unlabeled_image.dtype == torch.float32 and labeled_image.dim() == 4 and \
+                labeled_image.shape[1:] == unlabeled_image.shape[1:] and labeled_image.is_cuda:
+            if not keep_unflipped:
+                return ops.cat_flipped(labeled_image, unlabeled_image, flips)
+            net = getattr(self._model, "module", self._model)
+            return ops.cat_flip(labeled_image, unlabeled_image, flips,
+                                stem_dtype=getattr(net, "compute_dtype", None) if getattr(net, "input_dim", None) == 1 else None)
+        flipped = ops.flip(unlabeled_image, flips)
+        return torch.cat([labeled_image, unlabeled_image, flipped] if keep_unflipped else [labeled_image, flipped], dim=0)
+
     def _device_step(self, labeled_image: Tensor, labeled_target: Tensor, unlabeled_image: Tensor, flips2: Tensor, seed: int = None):
         """Everything of the iteration that runs on the GPU between the upload and the read-back: forward, losses, backward,
         optimiser kernel, Dice counts.  No host synchronisation, no host->device traffic, and -- for the shipped trainers -- no launch
@@ -471,31 +502,15 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         lb, ub = len(labeled_image), len(unlabeled_image)
         self._flips2 = flips2
         flips = flips2[:ub]
-        if labeled_image.dtype == unlabeled_image.dtype == torch.float32 and labeled_image.dim() == 4 and \
-                labeled_image.shape[1:] == unlabeled_image.shape[1:] and labeled_image.is_cuda:
-            # [labeled | unlabeled | flip(unlabeled)] in one launch (ref :148-153: per-sample flips, stack, cat)
-            net = getattr(self._model, "module", self._model)
-            batch = ops.cat_flip(labeled_image, unlabeled_image, flips,
-                                 stem_dtype=getattr(net, "compute_dtype", None) if getattr(net, "input_dim", None) == 1 else None)
-            unlabeled_image_tf = batch[lb + ub:]
-        else:
-            unlabeled_image_tf = ops.flip(unlabeled_image, flips)
-            batch = torch.cat([labeled_image, unlabeled_image, unlabeled_image_tf], dim=0)
+        batch = self._assemble(labeled_image, unlabeled_image, flips, keep_unflipped=True)
+        unlabeled_image_tf = batch[lb + ub:]
         assert unlabeled_image_tf.shape == unlabeled_image.shape
 
-        with checks.deferred(self._pending.checks):   # simplex / NaN assertions are raised at this iteration's fetch()
-            self._before_forward(ub)
-            try:
-                predict_logits = self._model(batch)
-            finally:
-                self._after_forward()
+        predict_logits = self._forward(batch, ub)
         label_logits, unlabel_logits, unlabel_tf_logits = ops.split_rows(predict_logits, [lb, ub, ub])
         labels = labeled_target.squeeze(1)
         with checks.deferred(self._pending.checks):
-            if isinstance(self._sup_criterion, KL_div) and self._sup_criterion.supports_fused():
-                sup_loss = self._sup_criterion.from_logits(label_logits, labels)
-            else:
-                sup_loss = self._sup_criterion(label_logits.softmax(1), class2one_hot(labels, self.num_classes))
+            sup_loss = supervised_loss(self._sup_criterion, label_logits, labels, self.num_classes)
             reg_fn = self.regularization
             fused = getattr(reg_fn, "_miseg_fused", False)
             reg_loss = reg_fn(
@@ -603,9 +618,10 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         self._record(host, inter.clone(), union.clone(), label_group)   # the meters keep them; the pinned ring is reused
 
     def _record(self, host: dict, inter: Tensor, union: Tensor, label_group) -> None:
-        self.meters["sup_loss"].add(host["sup_loss"])
+        for name in self.meters.meter_names:
+            if name in host:
+                self.meters[name].add(host[name])
         self.meters["sup_dice"].add_counts(inter, union, group_name=label_group)
-        self.meters["reg_loss"].add(host["reg_loss"])
 
     @staticmethod
     def _unzip_data(data, device):
@@ -617,7 +633,18 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         return LinearLoss([])      # symbolic zero (ref :194-197 returns a zero tensor): no kernel, reported as 0
 
 
-class UDATrainEpocher(TrainEpocher):
+class _uda_mixin:
+    """The reported consistency term of ``uda``, ``midl`` and ``udaiic`` (``_reg_criterion`` is the epocher's)."""
+
+    METERS = ("uda",)
+
+    def _uda(self, unlabeled_tf_logits: Tensor, unlabeled_logits: Tensor, flips: Tensor):
+        loss = consistency_loss(self._reg_criterion, unlabeled_tf_logits, unlabeled_logits, flips)
+        self._pending.put("uda", loss)
+        return loss
+
+
+class UDATrainEpocher(_uda_mixin, TrainEpocher):
     """Consistency between f(flip(x)) and flip(f(x)).detach() (ref :200-226)."""
 
     def __init__(self, model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_criterion: T_loss, reg_weight: float,
@@ -626,40 +653,16 @@ class UDATrainEpocher(TrainEpocher):
                          device, feature_position, feature_importance)
         self._reg_criterion = reg_criterion
 
-    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
-        meters = super()._configure_meters(meters)
-        meters.register_meter("uda", AverageValueMeter())
-        return meters
-
-    def _uda(self, unlabeled_tf_logits: Tensor, unlabeled_logits: Tensor, flips: Tensor) -> Tensor:
-        if isinstance(self._reg_criterion, nn.MSELoss):
-            loss = LinearLoss.of(ops.softmax_mse(unlabeled_tf_logits, unlabeled_logits, flips))  # flip + 2 softmaxes + MSE fused
-        elif isinstance(self._reg_criterion, KL_div) and self._reg_criterion.supports_fused():   # `UDARegCriterion.name: kl`
-            loss = LinearLoss.of(ops.softmax_kl_consistency(unlabeled_tf_logits, unlabeled_logits, flips))
-        else:  # any other criterion object: called as the reference calls it, on materialised operands
-            loss = self._reg_criterion(unlabeled_tf_logits.softmax(1), ops.flip(unlabeled_logits, flips).softmax(1).detach())
-        self._pending.put("uda", loss)
-        return loss
-
     @_fused
     def regularization(self, unlabeled_tf_logits: Tensor, unlabeled_logits_tf: Tensor = None, seed=None, *args,
                        unlabeled_logits: Tensor = None, flips: Tensor = None, **kwargs):
         return self._uda(unlabeled_tf_logits, unlabeled_logits, flips)
 
-    def _record(self, host, inter, union, label_group):
-        super()._record(host, inter, union, label_group)
-        if "uda" in host:
-            self.meters["uda"].add(host["uda"])
-
 
 class IICTrainEpocher(TrainEpocher):
     """Global (encoder taps) + local (decoder taps) IIC mutual information (ref :229-284)."""
 
-    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
-        meters = super()._configure_meters(meters)
-        meters.register_meter("mi", AverageValueMeter())
-        meters.register_meter("individual_mis", MultipleAverageValueMeter())
-        return meters
+    METERS = ("mi", "individual_mis")
 
     def __init__(self, model, projectors_wrapper: ProjectorWrapper, optimizer, labeled_loader, unlabeled_loader, sup_criterion,
                  IIDSegCriterionWrapper: IICLossWrapper, reg_weight: float, num_batches: int, cur_epoch: int = 0, device="cpu",
@@ -767,11 +770,10 @@ class IICTrainEpocher(TrainEpocher):
     def _record(self, host, inter, union, label_group):
         super()._record(host, inter, union, label_group)
         if "mi" in host:
-            self.meters["mi"].add(host["mi"])
             self.meters["individual_mis"].add(**{n: host["mi/" + n] for n in self._feature_position})
 
 
-class UDAIICEpocher(IICTrainEpocher):
+class UDAIICEpocher(_uda_mixin, IICTrainEpocher):
     """``cons_weight * UDA + iic_weight * IIC`` with reg_weight forced to 1 (ref :287-323)."""
 
     def __init__(self, model, projectors_wrapper: ProjectorWrapper, optimizer, labeled_loader, unlabeled_loader, sup_criterion,
@@ -782,13 +784,7 @@ class UDAIICEpocher(IICTrainEpocher):
         self._cons_weight, self._iic_weight = cons_weight, iic_weight
         self._reg_criterion = reg_criterion
 
-    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
-        meters = super()._configure_meters(meters)
-        for name in ("uda", "iic_weight", "uda_weight"):
-            meters.register_meter(name, AverageValueMeter())
-        return meters
-
-    _uda = UDATrainEpocher._uda
+    METERS = ("iic_weight", "uda_weight")
 
     @_fused
     def regularization(self, unlabeled_tf_logits: Tensor, unlabeled_logits_tf: Tensor = None, seed: int = None, *args,
@@ -799,7 +795,6 @@ class UDAIICEpocher(IICTrainEpocher):
 
     def _record(self, host, inter, union, label_group):
         super()._record(host, inter, union, label_group)
-        self.meters["uda"].add(host["uda"])
         # host-side bookkeeping lives here, not in regularization(): that one is part of the captured device step
         self.meters["iic_weight"].add(self._iic_weight)
         self.meters["uda_weight"].add(self._cons_weight)
@@ -823,6 +818,7 @@ class MeanTeacherEpocher(TrainEpocher):
     them; the block has accumulator room for both training forwards."""
 
     _TRAIN_FORWARDS = 2
+    METERS = ("reg_weight",)
 
     def __init__(self, model, teacher_model, optimizer, labeled_loader: T_loader, unlabeled_loader: T_loader, sup_criterion: T_loss,
                  reg_criterion: T_loss, reg_weight: float, num_batches: int, cur_epoch=0, device="cpu", feature_position=None,
@@ -834,11 +830,6 @@ class MeanTeacherEpocher(TrainEpocher):
         self._reg_criterion = reg_criterion
         self._ema_updater = ema_updater
         self._ema_row = None
-
-    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
-        meters = super()._configure_meters(meters)
-        meters.register_meter("reg_weight", AverageValueMeter())
-        return meters
 
     def _run(self, *args, **kwargs) -> EpochResultDict:
         self._teacher_model.train()
@@ -867,26 +858,15 @@ class MeanTeacherEpocher(TrainEpocher):
         lb, ub = len(labeled_image), len(unlabeled_image)
         self._flips2 = flips2
         flips = flips2[:ub]
-        if labeled_image.dtype == unlabeled_image.dtype == torch.float32 and labeled_image.dim() == 4 and \
-                labeled_image.shape[1:] == unlabeled_image.shape[1:] and labeled_image.is_cuda:
-            batch = ops.cat_flipped(labeled_image, unlabeled_image, flips)      # [labeled | flip(unlabeled)] (ref :176-181)
-        else:
-            batch = torch.cat([labeled_image, ops.flip(unlabeled_image, flips)], dim=0)
+        batch = self._assemble(labeled_image, unlabeled_image, flips, keep_unflipped=False)      # [labeled | flip(unlabeled)] (ref :176-181)
         with checks.deferred(self._pending.checks):
             with torch.no_grad():          # the teacher: train mode, its own batch statistics, no autograd (ref :187-188)
                 teacher_logits = self._teacher_model(unlabeled_image)
-            self._before_forward(ub)
-            try:
-                predict_logits = self._model(batch)
-            finally:
-                self._after_forward()
+            predict_logits = self._forward(batch, ub)
         label_logits, unlabel_tf_logits = ops.split_rows(predict_logits, [lb, ub])
         labels = labeled_target.squeeze(1)
         with checks.deferred(self._pending.checks):
-            if isinstance(self._sup_criterion, KL_div) and self._sup_criterion.supports_fused():
-                sup_loss = self._sup_criterion.from_logits(label_logits, labels)
-            else:
-                sup_loss = self._sup_criterion(label_logits.softmax(1), class2one_hot(labels, self.num_classes))
+            sup_loss = supervised_loss(self._sup_criterion, label_logits, labels, self.num_classes)
             reg_loss = self._consistency(unlabel_tf_logits, teacher_logits, flips)
         inter, union = self._finish_step(sup_loss, reg_loss, label_logits, labels)
         # the EMA after Adam (ref :205-206), guarded by the flags that guarded Adam
@@ -896,11 +876,7 @@ class MeanTeacherEpocher(TrainEpocher):
 
     def _consistency(self, student_tf_logits: Tensor, teacher_logits: Tensor, flips: Tensor):
         """``reg_criterion(softmax(student(flip(u))), softmax(flip(teacher(u))).detach())`` (ref :193-194)."""
-        if isinstance(self._reg_criterion, nn.MSELoss):
-            return LinearLoss.of(ops.softmax_mse(student_tf_logits, teacher_logits, flips))
-        if isinstance(self._reg_criterion, KL_div) and self._reg_criterion.supports_fused():
-            return LinearLoss.of(ops.softmax_kl_consistency(student_tf_logits, teacher_logits, flips))
-        return self._reg_criterion(student_tf_logits.softmax(1), ops.flip(teacher_logits, flips).softmax(1).detach())
+        return consistency_loss(self._reg_criterion, student_tf_logits, teacher_logits, flips)
 
 
 class MIDLTrainEpocher(UDATrainEpocher):
@@ -916,6 +892,8 @@ class MIDLTrainEpocher(UDATrainEpocher):
     composition -- torch softmax and this repo's generic ``IIDSegmentationSmallPathLoss`` -- eagerly: the launch tape then declines
     with its usual warning.  Meters: the base ones, ``uda`` and ``mi`` (= -MI loss, the sign ``IICTrainEpocher`` reports)."""
 
+    METERS = ("mi",)
+
     def __init__(self, model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_criterion: T_loss, num_batches: int,
                  cur_epoch: int = 0, device="cpu", feature_position=None, feature_importance=None, cons_weight: float = 5.0,
                  iic_weight: float = 0.1, padding: int = 1, patch_size=1024) -> None:
@@ -924,11 +902,6 @@ class MIDLTrainEpocher(UDATrainEpocher):
         from contrastyou.losses.iic_loss import IIDSegmentationSmallPathLoss
         self._cons_weight, self._iic_weight = float(cons_weight), float(iic_weight)
         self._mi_criterion = IIDSegmentationSmallPathLoss(lamda=1.0, padding=int(padding), patch_size=patch_size)
-
-    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
-        meters = super()._configure_meters(meters)
-        meters.register_meter("mi", AverageValueMeter())
-        return meters
 
     def windows(self, h: int, w: int):
         """The criterion's patches of an h x w map, (h0, h1, w0, w1) in the reference's order (patch_generator)."""
@@ -961,11 +934,6 @@ class MIDLTrainEpocher(UDATrainEpocher):
         crit = self._mi_criterion
         return super()._tape_signature() + (self._iic_weight, crit.padding, crit.lamda, tuple(crit._patch_size), tuple(crit._step_size))
 
-    def _record(self, host, inter, union, label_group):
-        super()._record(host, inter, union, label_group)
-        if "mi" in host:
-            self.meters["mi"].add(host["mi"])
-
 
 class EntropyMinEpocher(TrainEpocher):
     """``entmin``: the ``partial`` iteration (same flips, same ``[labeled | unlabeled | flip(unlabeled)]`` forward, same supervised
@@ -980,16 +948,13 @@ class EntropyMinEpocher(TrainEpocher):
     eagerly: the launch tape then declines with its usual warning.  Meters: the base ones plus ``entropy``, the unweighted value
     (``reg_loss`` reports the same number, as ``uda``'s does)."""
 
+    METERS = ("entropy",)
+
     def __init__(self, model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_weight: float, num_batches: int,
                  cur_epoch: int = 0, device="cpu", feature_position=None, feature_importance=None) -> None:
         super().__init__(model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_weight, num_batches, cur_epoch,
                          device, feature_position, feature_importance)
         self._entropy_criterion = Entropy()
-
-    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
-        meters = super()._configure_meters(meters)
-        meters.register_meter("entropy", AverageValueMeter())
-        return meters
 
     @_fused
     def regularization(self, unlabeled_tf_logits: Tensor, unlabeled_logits_tf: Tensor = None, seed=None, *args,
@@ -1001,11 +966,6 @@ class EntropyMinEpocher(TrainEpocher):
             loss = crit(ops.flip(unlabeled_logits, flips).float().softmax(1))
         self._pending.put("entropy", loss)
         return loss
-
-    def _record(self, host, inter, union, label_group):
-        super()._record(host, inter, union, label_group)
-        if "entropy" in host:
-            self.meters["entropy"].add(host["entropy"])
 
 
 class VATEpocher(TrainEpocher):
@@ -1030,6 +990,7 @@ class VATEpocher(TrainEpocher):
     ``reg_weight``."""
 
     _TAPE_DEFAULT = False
+    METERS = ("reg_weight",)
 
     def __init__(self, model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_weight: float, num_batches: int,
                  cur_epoch: int = 0, device="cpu", feature_position=None, feature_importance=None, xi: float = 10.0, eps: float = 1.0,
@@ -1042,11 +1003,6 @@ class VATEpocher(TrainEpocher):
     def enable_step_tape(self, warmup: int = 3) -> None:
         """No-op: the ``vat`` iteration runs eagerly (class docstring)."""
 
-    def _configure_meters(self, meters: MeterInterface) -> MeterInterface:
-        meters = super()._configure_meters(meters)
-        meters.register_meter("reg_weight", AverageValueMeter())
-        return meters
-
     def _run(self, *args, **kwargs) -> EpochResultDict:
         self.meters["reg_weight"].add(self._reg_weight)
         return super()._run(*args, **kwargs)
@@ -1056,15 +1012,8 @@ class VATEpocher(TrainEpocher):
         self._flips2 = flips2
         labels = labeled_target.squeeze(1)
         with checks.deferred(self._pending.checks):
-            self._before_forward(len(unlabeled_image))
-            try:
-                label_logits = self._model(labeled_image)
-            finally:
-                self._after_forward()
-            if isinstance(self._sup_criterion, KL_div) and self._sup_criterion.supports_fused():
-                sup_loss = self._sup_criterion.from_logits(label_logits, labels)
-            else:
-                sup_loss = self._sup_criterion(label_logits.softmax(1), class2one_hot(labels, self.num_classes))
+            label_logits = self._forward(labeled_image, len(unlabeled_image))
+            sup_loss = supervised_loss(self._sup_criterion, label_logits, labels, self.num_classes)
             lds, _, _ = self._vat(self._model, unlabeled_image, seed=seed)
         return self._finish_step(LinearLoss.of(sup_loss), LinearLoss.of(lds), label_logits, labels)
 

@@ -60,6 +60,7 @@ class SemiTrainer(Trainer):
 
     RUN_PATH = str(Path(PROJECT_PATH) / "semi_seg" / "runs")  # noqa
     feature_positions = ["Up_conv4", "Up_conv3"]
+    SINGLE_PROCESS: Optional[str] = None     # why the trainer refuses data-parallel runs, worded after its ``NAME`` (None: it takes them)
 
     def __init__(self, *, model: nn.Module, labeled_loader: T_loader, unlabeled_loader: T_loader, val_loader: T_loader,
                  test_loader: T_loader, sup_criterion: T_loss, save_dir: str = "base", max_epoch: int = 100,
@@ -113,9 +114,20 @@ class SemiTrainer(Trainer):
 
     def attach_data_parallel(self, num_buckets: int = 3):
         """One process per GPU: bucketed RCCL all-reduce of the flat gradient, launched from autograd hooks
-        (``miseg_amd.ddp``).  No-op (returns None) when torch.distributed is not initialised or has a single rank."""
+        (``miseg_amd.ddp``).  No-op (returns None) when torch.distributed is not initialised or has a single rank.  A trainer with a
+        ``SINGLE_PROCESS`` reason refuses a multi-rank run."""
+        if self.SINGLE_PROCESS is not None:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise RuntimeError(f"Trainer.name={self.NAME} runs in a single process: {self.SINGLE_PROCESS}")
+            return None
         from miseg_amd import ddp
         return ddp.attach(self, num_buckets=num_buckets)
+
+    def _refuse_float16(self) -> None:
+        """For the trainers that say in ``NO_FLOAT16`` what they lack for ``Arch.compute_dtype=float16``; called from their ``_init``."""
+        if getattr(self._model, "compute_dtype", torch.float32) == torch.float16:
+            raise NotImplementedError(f"Trainer.name={self.NAME} {self.NO_FLOAT16}: use Arch.compute_dtype float32 or bfloat16")
 
     # ------------------------------------------------------------------ one epoch
     def _epoch_args(self) -> dict:
@@ -132,7 +144,7 @@ class SemiTrainer(Trainer):
         return epocher.run()
 
     def _eval_epoch(self, *, loader: T_loader, **kwargs) -> Tuple[EpochResultDict, float]:
-        return E.EvalEpocher(self._model, val_loader=loader, sup_criterion=self._sup_criterion, cur_epoch=self._cur_epoch,
+        return E.EvalEpocher(self._inference_model(), val_loader=loader, sup_criterion=self._sup_criterion, cur_epoch=self._cur_epoch,
                              device=self._device).run()
 
     # ------------------------------------------------------------------ the loop
@@ -161,6 +173,7 @@ class SemiTrainer(Trainer):
 
     # ------------------------------------------------------------------ inference
     def _inference_model(self) -> nn.Module:
+        """The network that validation, test and ``inference`` evaluate."""
         return self._model
 
     def inference(self, checkpoint=None, surface_metrics=None, keep_largest=None):  # noqa
@@ -262,10 +275,6 @@ class MeanTeacherTrainer(SemiTrainer):
                                     self._sup_criterion, reg_criterion=self._reg_criterion, reg_weight=self._reg_weight,
                                     ema_updater=self._ema_updater, **self._epoch_args())
 
-    def _eval_epoch(self, *, loader: T_loader, **kwargs) -> Tuple[EpochResultDict, float]:
-        return E.EvalEpocher(self._teacher_model, val_loader=loader, sup_criterion=self._sup_criterion, cur_epoch=self._cur_epoch,
-                             device=self._device).run()
-
     def _inference_model(self):
         return self._teacher_model
 
@@ -319,6 +328,9 @@ class VATTrainer(SemiTrainer):
     data-parallel runs.  Semantics: DESIGN.md section 23."""
 
     DEFAULTS = dict(weight=1.0, xi=10.0, eps=1.0, prop_eps=0.25, ip=1)
+    NAME = "vat"
+    NO_FLOAT16 = "has no loss scaling in its direction pass"
+    SINGLE_PROCESS = "the gradient reducer's hooks would also fire in the direction pass"
 
     @classmethod
     def parameters(cls, configuration) -> dict:
@@ -333,17 +345,10 @@ class VATTrainer(SemiTrainer):
 
     def _init(self) -> None:
         super()._init()
-        if getattr(self._model, "compute_dtype", torch.float32) == torch.float16:
-            raise NotImplementedError("Trainer.name=vat has no loss scaling in its direction pass: use Arch.compute_dtype float32 or bfloat16")
+        self._refuse_float16()
         params = self.parameters(self._config)
         self._reg_weight = params.pop("weight")
         self._vat_params = params
-
-    def attach_data_parallel(self, num_buckets: int = 3):
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise RuntimeError("Trainer.name=vat runs in a single process: the gradient reducer's hooks would also fire in the direction pass")
-        return None
 
     def _make_epocher(self):
         return E.VATEpocher(self._model, self._optimizer, self._labeled_loader, self._unlabeled_loader, self._sup_criterion,
@@ -364,6 +369,8 @@ class ContrastTrainer(SemiTrainer):
     DEFAULTS = Path(PROJECT_PATH) / "config" / "contrast.yaml"
     SECTION = "ContrastParameters"
     NAME, STAGE = "contrast", "encoder"
+    NO_FLOAT16 = "has no loss scaling"
+    SINGLE_PROCESS = "a cross-rank contrastive loss needs an all-gather of the embeddings, which is not implemented"
 
     def __init__(self, *, configuration=None, **kwargs):
         import yaml
@@ -371,10 +378,6 @@ class ContrastTrainer(SemiTrainer):
         configuration = dict(configuration or {})
         configuration[self.SECTION] = {**shipped, **(configuration.get(self.SECTION) or {})}
         super().__init__(configuration=configuration, **kwargs)
-
-    def _refuse_float16(self) -> None:
-        if getattr(self._model, "compute_dtype", torch.float32) == torch.float16:
-            raise NotImplementedError(f"Trainer.name={self.NAME} has no loss scaling: use Arch.compute_dtype float32 or bfloat16")
 
     def _init(self) -> None:
         super()._init()
@@ -399,13 +402,6 @@ class ContrastTrainer(SemiTrainer):
         ``grad is None`` to skip the rest; the flat fused Adam zero-fills such slots and would still decay them."""
         blocks = self._model._range("Conv1", self._extract_position)
         return chain(*(getattr(self._model, name).parameters() for name in blocks), self._projector.parameters())
-
-    def attach_data_parallel(self, num_buckets: int = 3):
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise RuntimeError(f"Trainer.name={self.NAME} runs in a single process: a cross-rank contrastive loss needs an all-gather of the "
-                               "embeddings, which is not implemented")
-        return None
 
     def _make_epocher(self):
         return E.PretrainEncoderEpocher(self._model, self._projector, self._optimizer, self._unlabeled_loader, self._contrastive_criterion,

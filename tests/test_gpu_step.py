@@ -894,3 +894,61 @@ def test_cfg4_step_matches_the_oracle(monkeypatch, dtype, mi_precision):
         # measured: logits layer 3.4e-3 / 1.3e-3, decoder-tap heads 1.7e-3 .. 1.2e-2
         assert max(v for k, v in dec.items() if k.startswith("DeConv_1x1")) < 1e-2, dec
         assert max(dec.values()) < 4e-2, {k: v for k, v in dec.items() if v >= 4e-2}
+
+
+def _one_eager_iteration(trainer, fused):
+    """One eager fp32 iteration (launch tape off) of ``trainer`` at LB = UB = 2, 32 x 32, 4 classes, from fixed weights, batches and
+    flip draws; ``fused=False`` swaps in a ``KL_div`` that declines its kernel.  -> (the epoch's sup_loss, parameters before, after)."""
+    from contrastyou.arch import UNet
+    from deepclustering2.loss import KL_div
+    from deepclustering2.models import ema_updater
+    from deepclustering2.optim import Adam
+    from semi_seg import epocher as E
+    from semi_seg.synthetic import SyntheticPairs
+
+    class UnfusedKL(KL_div):
+        def supports_fused(self):
+            return False
+
+    def unet(seed):
+        net = UNet(1, 4, compute_dtype="float32")
+        net.load_state_dict(OU.init_state(1, 4, seed=seed))
+        return net.to(DEV)
+
+    model = unet(61)
+    opt = Adam(model.parameters(), lr=STEP["lr"], weight_decay=STEP["wd"])
+    kl = (KL_div if fused else UnfusedKL)(verbose=False)
+    lab, unl = iter(SyntheticPairs(2, 32, 4, seed=7, pool=1, device=DEV)), iter(SyntheticPairs(2, 32, 4, seed=8, pool=1, device=DEV))
+    common = dict(num_batches=1, cur_epoch=0, device=DEV, feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25])
+    if trainer == "meanteacher":
+        teacher = unet(62)
+        for p in teacher.parameters():
+            p.detach_().requires_grad_(False)
+        ep = E.MeanTeacherEpocher(model, teacher, opt, lab, unl, kl, torch.nn.MSELoss(), 10.0,
+                                  ema_updater=ema_updater(alpha=0.999, justify_alpha=True, weight_decay=1e-6), **common)
+    elif trainer == "vat":
+        ep = E.VATEpocher(model, opt, lab, unl, kl, 1.0, **common)
+    else:
+        ep = E.TrainEpocher(model, opt, lab, unl, kl, 0, **common)
+    ep._TAPE_DEFAULT = False
+    opt.flat.ensure()
+    before = opt.flat.flat_param.detach().clone()
+    random.seed(4321)
+    res = ep.run()
+    assert ep._step_tape is None
+    return res["sup_loss"]["mean"], before, opt.flat.flat_param.detach().clone()
+
+
+@pytest.mark.parametrize("trainer", ["partial", "meanteacher", "vat"])
+def test_unfused_supervised_loss_on_the_device(trainer):
+    """A supervised criterion without the fused kernel (``semi_seg.epocher.supervised_loss``'s second branch: torch softmax,
+    ``class2one_hot``, the criterion's own expression and autograd through them) in the three iterations that compute the
+    supervised loss themselves: the reported ``sup_loss`` is the fused kernel's on the same weights and batch -- to the tolerance
+    test_gpu_losses.py::test_softmax_kl_vs_golden holds that kernel to -- and the optimiser has run."""
+    fused, _, _ = _one_eager_iteration(trainer, True)
+    unfused, before, after = _one_eager_iteration(trainer, False)
+    print(f"{trainer}: sup_loss fused {fused!r} unfused {unfused!r} rel {abs(fused - unfused) / abs(fused):.3e}, "
+          f"largest parameter move {float((after - before).abs().max()):.3e}")
+    np.testing.assert_allclose(unfused, fused, rtol=1e-5)
+    assert fused > 0 and bool(torch.isfinite(after).all())
+    assert not torch.equal(before, after)
