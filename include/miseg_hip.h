@@ -336,6 +336,21 @@ int miseg_softmax_kl(void* stream, const float* logits, const int64_t* labels, i
 int miseg_softmax_mse(void* stream, const float* a, const float* b, const int32_t* flips, int64_t N, int64_t H,
                       int64_t W, int64_t C, const float* upstream, float* loss, float* ga, void* ws,
                       int64_t ws_bytes);
+/* softmax_dice: the Generalized Dice loss of whl:deepclustering2/loss/dice_loss.py:79-135 (reduction "mean", no ignore_index) on
+ * softmax(logits), the one-hot taken from int64 labels [N,H,W], optionally plus the KL term of softmax_kl (library version 416):
+ *   I[n,c] = sum_px p_c [label == c],  D[n,c] = sum_px p_c^pow + #(label == c),  GDL = mean_{n,c} w_c (1 - (2 I + eps) / (D + eps)),
+ *   loss = kl_weight * KL + dice_weight * GDL   (kl_weight == 0: the KL part is neither computed nor added),
+ *   glogits (may be NULL: forward only, one launch less) = upstream * d loss / d logits.
+ * pow in {1, 2}; class_weight = device fp32[C] or NULL (all ones).  Class counts 2-6, 8, 10, 16; any other count, another pow, an empty
+ * batch, a null logits / labels / loss / bad_label / ws or a workspace below miseg_softmax_dice_ws_bytes returns MISEG_E_INVALID and
+ * launches nothing.  A label outside [0,C) sets *bad_label (never cleared here); that pixel adds to none of I, D and KL, the divisors
+ * stay N*C and N*H*W, and its C entries of glogits are written as 0.  Three launches (per-block partials, one finishing block that
+ * sums them in double in a fixed order, the gradient pass), no atomics: two calls give the same bits, and a forward-only call the
+ * same loss bits as one that writes the gradient. */
+int64_t miseg_softmax_dice_ws_bytes(int64_t N, int64_t H, int64_t W, int64_t C);
+int miseg_softmax_dice(void* stream, const float* logits, const int64_t* labels, int64_t N, int64_t H, int64_t W, int64_t C,
+                       int pow, float eps, const float* class_weight, float kl_weight, float dice_weight,
+                       const float* upstream, float* loss, float* glogits, int32_t* bad_label, void* ws, int64_t ws_bytes);
 /* per-sample H/W flip of an [N,C,H,W]-indexed tensor with arbitrary element strides (in elements),
  * elem_bytes in {2,4,8}; ref whl:deepclustering2/augment/tensor_augment.py:31-39. Bit-exact.
  * in_strides4 / out_strides4 are HOST arrays of 4 strides (read at launch time); in, out and flips are device pointers. */

@@ -958,6 +958,63 @@ def softmax_entropy(logits: Tensor) -> Tensor:
     return _SoftmaxEntropy.apply(logits)
 
 
+def softmax_dice_supported(c: int) -> bool:
+    """Whether ``softmax_dice`` has a kernel for ``c`` classes (the pixel losses' dispatch list: 2-6, 8, 10, 16)."""
+    return int(c) in _LOSS_CLASS_COUNTS
+
+
+class _SoftmaxDice(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits: Tensor, labels: Tensor, flag_box: list, consts: tuple, class_weight: Optional[Tensor], want_grad: bool):
+        _need_gpu(logits, labels, class_weight)
+        raw_logits = logits
+        logits = _logits_nhwc(logits)
+        n, c, h, w = logits.shape
+        labels = labels.contiguous().view(n, h, w)
+        if labels.dtype != torch.int64:
+            labels = labels.long()
+        dev = logits.device
+        power, eps, kl_weight, dice_weight = consts
+        loss = scalar_out((), dev)
+        glogits = empty_nhwc(n, c, h, w, torch.float32, dev) if want_grad else None      # evaluation: forward only, no gradient pass
+        bad = zero_counter(dev, (1,))
+        ws = _ws(query("miseg_softmax_dice_ws_bytes", n, h, w, c), dev)
+        call("miseg_softmax_dice", _stream(), _ptr(logits), _ptr(labels), n, h, w, c, power, eps, _ptr(class_weight), kl_weight,
+             dice_weight, None, _ptr(loss), _ptr(glogits), _ptr(bad), _ptr(ws), ws.numel())
+        if want_grad:
+            ctx.save_for_backward(glogits)
+        ctx.part = _split_part_of(raw_logits, logits)
+        flag_box.append(bad)      # the bad-label flag, handed over beside the graph as in _SoftmaxKL
+        return loss
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (glogits,) = ctx.saved_tensors
+        return _scaled_grad(ctx.part, glogits, g), None, None, None, None, None
+
+
+def softmax_dice(logits: Tensor, labels: Tensor, *, pow: int = 1, eps: float = 1e-8, class_weight: Optional[Tensor] = None,
+                 kl_weight: float = 0.0, dice_weight: float = 1.0, check_labels: bool = True) -> Tensor:
+    """``kl_weight * KL_div()(p, t) + dice_weight * GeneralizedDiceLoss(eps, class_weight, pow)(p, t)`` for ``p = softmax(logits, 1)``
+    and ``t = class2one_hot(labels)``, reduction 'mean', in the fused entry point ``miseg_softmax_dice`` with its backward (with
+    ``kl_weight == 0`` the KL part is not computed).  ``class_weight``: a float32 vector of C entries on the logits' device (the
+    criterion objects upload theirs once), or None.  Under ``torch.no_grad()`` the gradient pass is not launched.  A label outside
+    [0, C) is flagged, adds nothing and gets a zero gradient; with ``check_labels`` the flag goes to ``checks.require_zero`` exactly
+    as in ``softmax_kl``.  Class counts: ``softmax_dice_supported``."""
+    if class_weight is not None:
+        assert class_weight.dtype == torch.float32 and class_weight.is_contiguous() and class_weight.numel() == int(logits.shape[1]), \
+            (class_weight.dtype, tuple(class_weight.shape), int(logits.shape[1]))
+    flag_box: list = []
+    want_grad = torch.is_grad_enabled() and logits.requires_grad
+    loss = _SoftmaxDice.apply(logits, labels, flag_box, (int(pow), float(eps), float(kl_weight), float(dice_weight)), class_weight, want_grad)
+    bad = flag_box[0]
+    if check_labels:
+        from . import checks
+        checks.require_zero(bad, AssertionError, f"softmax_dice: a label lies outside [0, {int(logits.shape[1])}) "
+                                                 f"(class2one_hot of the {int(logits.shape[1])}-class configuration would refuse it)")
+    return loss
+
+
 _SUPCON_MAX_N, _SUPCON_MAX_D = 1024, 1024     # kSupMaxN / kSupMaxD of csrc/supcon.hip
 
 

@@ -197,3 +197,68 @@ class IICLossWrapper(nn.Module):
     @property
     def feature_names(self) -> List[str]:
         return self._encoder_features + self._decoder_features
+
+
+class KLDiceLoss(nn.Module):
+    """``kl_weight * KL_div()(p, t) + dice_weight * dice(p, t)`` -- the project's own combination of the two supervised criteria of
+    ``deepclustering2.loss`` (the wheel has no combined one).  Called on materialised operands like either part;
+    ``from_logits`` is the fused entry point ``miseg_softmax_dice``, which evaluates both terms from the logits in one call."""
+
+    def __init__(self, kl_weight: float = 1.0, dice_weight: float = 1.0, dice=None) -> None:
+        super().__init__()
+        from deepclustering2.loss import GeneralizedDiceLoss, KL_div
+        self.kl_weight, self.dice_weight = float(kl_weight), float(dice_weight)
+        self._kl = KL_div(verbose=False)
+        self._dice = GeneralizedDiceLoss() if dice is None else dice
+
+    def forward(self, prob: Tensor, target: Tensor, **kwargs) -> Tensor:
+        return self.kl_weight * self._kl(prob, target, **kwargs) + self.dice_weight * self._dice(prob, target, **kwargs)
+
+    def supports_fused(self, num_classes: int = None) -> bool:
+        return self._kl.supports_fused() and self._dice.supports_fused(num_classes)
+
+    def from_logits(self, logits: Tensor, labels: Tensor) -> Tensor:
+        from miseg_amd import ops
+        assert self.supports_fused(logits.shape[1])
+        d = self._dice
+        return ops.softmax_dice(logits, labels, pow=int(d.pow), eps=float(d.epsilon), class_weight=d.class_weight_on(logits.device),
+                                kl_weight=self.kl_weight, dice_weight=self.dice_weight)
+
+    def signature(self) -> tuple:
+        return (self.kl_weight, self.dice_weight) + self._dice.signature()
+
+    # the two coefficients are the whole state (KL_div's own entries belong to a criterion that can carry class weights; this one's cannot)
+    def state_dict(self, *args, **kwargs):
+        return {"kl_weight": self.kl_weight, "dice_weight": self.dice_weight}
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        self.kl_weight, self.dice_weight = float(state_dict["kl_weight"]), float(state_dict["dice_weight"])
+
+
+SUP_CRITERION_DEFAULTS = {"name": "kl", "pow": 1, "epsilon": 1e-8, "class_weight": None, "kl_weight": 1.0, "dice_weight": 1.0}
+
+
+def build_sup_criterion(configuration, num_classes: int = None) -> nn.Module:
+    """The supervised criterion of a configuration's OPTIONAL ``SupCriterion`` section over the defaults (``name: kl | dice |
+    kldice``); unknown keys are an error.  Without the section, or with ``name: kl``, this is the plain ``KL_div()`` every trainer
+    has always been given."""
+    from deepclustering2.loss import GeneralizedDiceLoss, KL_div
+    section = dict((configuration or {}).get("SupCriterion") or {})
+    unknown = sorted(set(section) - set(SUP_CRITERION_DEFAULTS))
+    if unknown:
+        raise KeyError(f"SupCriterion: unknown keys {unknown}; known: {sorted(SUP_CRITERION_DEFAULTS)}")
+    merged = {**SUP_CRITERION_DEFAULTS, **section}
+    name = str(merged["name"])
+    if name == "kl":
+        return KL_div()
+    if name not in ("dice", "kldice"):
+        raise KeyError(f"SupCriterion.name: {name!r}; known: ['dice', 'kl', 'kldice']")
+    weight = merged["class_weight"]
+    if weight is not None:
+        weight = [float(v) for v in weight]
+        if num_classes is not None and len(weight) != int(num_classes):
+            raise ValueError(f"SupCriterion.class_weight: {len(weight)} values for {num_classes} classes")
+    dice = GeneralizedDiceLoss(epsilon=float(merged["epsilon"]), weight=weight, pow=int(merged["pow"]))
+    if name == "dice":
+        return dice
+    return KLDiceLoss(kl_weight=float(merged["kl_weight"]), dice_weight=float(merged["dice_weight"]), dice=dice)

@@ -33,7 +33,7 @@ from contrastyou.trainer._utils import ClusterHead  # noqa
 from deepclustering2.augment.tensor_augment import TensorRandomFlip
 from deepclustering2.decorator import FixRandomSeed
 from deepclustering2.epoch import _Epocher  # noqa
-from deepclustering2.loss import Entropy, KL_div
+from deepclustering2.loss import Entropy, GeneralizedDiceLoss, KL_div
 from deepclustering2.meters2 import (AverageValueMeter, EpochResultDict, MeterInterface, MultipleAverageValueMeter, SurfaceMeter,
                                      UniversalDice)
 from deepclustering2.optim import get_lrs_from_optimizer
@@ -42,7 +42,7 @@ from deepclustering2.utils import class2one_hot
 from miseg_amd import checks, lazy, ops, stepio, unet_ops
 from miseg_amd.lazy import LinearLoss
 from miseg_amd.tape import keep as _keep
-from semi_seg._utils import FeatureExtractor, IICLossWrapper, ProjectorWrapper
+from semi_seg._utils import FeatureExtractor, IICLossWrapper, KLDiceLoss, ProjectorWrapper
 
 _DEBUG_ASSERTS = os.environ.get("MISEG_ASSERTS", "0") == "1"
 _READBACK_EARLY = os.environ.get("MISEG_READBACK_EARLY", "1") != "0"     # Dice counts + report launched before backward (0: after it, on the step's tail)
@@ -177,6 +177,9 @@ def supervised_loss(criterion: T_loss, logits: Tensor, labels: Tensor, num_class
     """``criterion(softmax(logits), one_hot(labels))`` (ref :165-166): one fused kernel where the criterion has it, else the
     reference's call on materialised operands.  ``disable_assert`` is the evaluation's (no autograd there for ``KL_div`` to insist on)."""
     if isinstance(criterion, KL_div) and criterion.supports_fused():
+        return criterion.from_logits(logits, labels)
+    if isinstance(criterion, (GeneralizedDiceLoss, KLDiceLoss)) and logits.is_cuda and criterion.supports_fused(logits.shape[1]) and \
+            ops.softmax_dice_supported(logits.shape[1]):
         return criterion.from_logits(logits, labels)
     flags = {"disable_assert": True} if disable_assert else {}
     return criterion(logits.softmax(1), class2one_hot(labels, num_classes), **flags)
@@ -413,8 +416,15 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         where += tuple(t.data_ptr() for name in ("_m", "_vmax") for t in getattr(opt, name, []) if t is not None)
         buf = next(iter(self._model.buffers()), None)
         return (type(self).__name__, float(self._reg_weight), getattr(self, "_cons_weight", None), getattr(self, "_iic_weight", None),
-                tuple(self._feature_importance), tuple(self._feature_position), type(self._sup_criterion).__name__,
+                tuple(self._feature_importance), tuple(self._feature_position), self._criterion_signature(self._sup_criterion),
                 type(getattr(self, "_reg_criterion", None)).__name__, where, None if buf is None else buf.data_ptr(), id(self._model))
+
+    @staticmethod
+    def _criterion_signature(criterion):
+        """A criterion's type name and, where it has a ``signature()``, the constants its fused call bakes into the recorded launch
+        (``GeneralizedDiceLoss`` / ``KLDiceLoss``: eps, pow, class weights, the two coefficients); ``KL_div`` has none."""
+        name = type(criterion).__name__
+        return (name, criterion.signature()) if hasattr(criterion, "signature") else name
 
     def _loss_scale(self) -> float:
         """Current loss scale: 1 unless the activations are IEEE half (BASELINE configs[4]); dynamic from its initial value."""

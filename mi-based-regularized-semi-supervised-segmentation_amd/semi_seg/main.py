@@ -15,6 +15,7 @@ from deepclustering2.loss import KL_div  # noqa: E402
 from deepclustering2.utils import gethash, set_benchmark  # noqa: E402
 from contrastyou import DATA_PATH  # noqa: E402
 from semi_seg.dataloader_helper import create_val_loader, get_dataloaders  # noqa: E402
+from semi_seg._utils import build_sup_criterion  # noqa: E402
 from semi_seg.synthetic import SyntheticEval, SyntheticPairs  # noqa: E402
 from semi_seg.trainer import trainer_zoos  # noqa: E402
 
@@ -80,12 +81,13 @@ def build_trainer(argv=None):
         unlabeled_loader = SyntheticPairs(config["UnlabeledData"]["batch_size"], size, classes, seed=2 * rank + 1)
         val_loader, test_loader = SyntheticEval(2, 4, size, classes, seed=100), SyntheticEval(2, 4, size, classes, seed=101)
     trainer_name = config["Trainer"].pop("name")
+    sup_criterion = build_sup_criterion(config, classes)      # the optional SupCriterion section; without it: KL_div()
     model = UNet(**config["Arch"])
     if pretrained is not None:
         load_pretrained(model, pretrained)
     trainer = trainer_zoos[trainer_name](
         model=model, labeled_loader=iter(labeled_loader), unlabeled_loader=iter(unlabeled_loader), val_loader=val_loader,
-        test_loader=test_loader, sup_criterion=KL_div(), configuration={**cmanager.config, **{"GITHASH": gethash(__file__)}},
+        test_loader=test_loader, sup_criterion=sup_criterion, configuration={**cmanager.config, **{"GITHASH": gethash(__file__)}},
         **config["Trainer"])
     trainer.init()
     if checkpoint is not None:
