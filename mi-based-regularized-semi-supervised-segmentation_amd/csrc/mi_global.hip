@@ -1,6 +1,6 @@
 // Global IIC mutual information (IIDLoss), all sub-heads per launch.  The encoder ClusterHead that feeds it is in heads_global.hip.
 // ref: contrastyou/losses/iic_loss.py:43-94.
-// These are latency-only ops (N<=64, K<=64): one small block per sub-head, fp32, fixed order.
+// These are latency-only ops (K <= 64, enforced; any N, a few dozen on the training path): one small block per sub-head, fp32, fixed order.
 #include "common.h"
 
 namespace miseg {
