@@ -64,8 +64,17 @@ int miseg_stream_wait_stream(void* waiter, void* producer);
  *   slot  = miseg_tape_bind(tape, base, span)  every recorded POINTER argument p in [base, base + span) is re-based at replay:
  *                                              p' = values[slot] + (p - base).  Bound are the loader's batch tensors, the pinned
  *                                              staging slots of miseg_upload / miseg_download, the event of miseg_event_record.
- *   miseg_tape_replay(tape, segment, values, nvalues)      nvalues = number of bindings; they are applied at segment 0
- *   miseg_tape_time_op / miseg_tape_timed_ms   HIP-event pair around one op at every replay, on the op's own stream
+ *   miseg_tape_replay(tape, segment, values, nvalues)      nvalues = number of bindings; they are applied at segment 0 ONLY, to
+ *                                              the ops of every segment: a replay of segment k > 0 ignores its `values` and
+ *                                              runs with what the last replay of segment 0 set.  A binding's span is half-open
+ *                                              (span < 1 counts as 1); slots are handed out in bind order, later ones win.
+ *   miseg_tape_time_op / miseg_tape_timed_ms   HIP-event pair around one op at every replay, on the op's own stream.  A read
+ *                                              returns the oldest min(cap, stored) samples and DROPS the rest: the next read
+ *                                              starts empty.
+ * Only the outermost call records (an entry point that forwards to others is one op), and a replay records nothing, whichever
+ * thread runs it and whatever tape is recording meanwhile.  A call the library REFUSES (MISEG_E_INVALID, nothing launched) is
+ * recorded like any other: every replay runs the ops before it, stops there with its status (miseg_last_error names the op
+ * index and the entry point) and runs nothing after it.
  * Everything else the recorded calls point at must stay where it is (the host keeps the recorded iteration's allocations in
  * a private pool).  Entry points that read HOST arrays during the call (miseg_flip's strides) record their own copy of them.
  * ------------------------------------------------------------------------------------------ */
