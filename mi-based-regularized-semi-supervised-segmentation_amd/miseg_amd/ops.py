@@ -272,10 +272,16 @@ class _LocalMI(torch.autograd.Function):
         return gx, gy, None, None, None, None
 
 
+# miseg_iic_local_loss_fwd gives each of its 16 waves 3 K^2 + 4 K floats of LDS and refuses above 156 KiB: K <= 28 fits
+# (tests/test_gpu_mi_loss.py pins 28 accepted / 29 refused).  The joint forward and the backward take K up to 32.
+LOCAL_LOSS_SINGLE_BLOCK_MAX_K = 28
+
+
 def _local_loss(raw: Tensor, k: int, pad: int, p: int, lamda: float, loss: Tensor, grad_raw: Tensor) -> None:
     """Loss epilogue of the local MI (ref iic_loss.py:124-146).  pad >= 2: one block per (window, displacement) -- the single
-    block per window needs ceil((2 pad + 1)^2 / 16) rounds on one CU while the IIC chain waits for it."""
-    if pad >= 2:
+    block per window needs ceil((2 pad + 1)^2 / 16) rounds on one CU while the IIC chain waits for it.  The same form whenever
+    the single block cannot hold K (it has no such limit; the numbers of grad_raw are the same bits either way)."""
+    if pad >= 2 or k > LOCAL_LOSS_SINGLE_BLOCK_MAX_K:
         ws = _ws(query("miseg_iic_local_loss_ws_bytes", pad, p), raw.device)
         call("miseg_iic_local_loss_fwd_ws", _stream(), _ptr(raw), k, pad, p, float(lamda), _ptr(loss), _ptr(grad_raw), _ptr(ws), ws.numel())
     else:
