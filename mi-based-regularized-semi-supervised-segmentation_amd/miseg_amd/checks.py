@@ -14,6 +14,7 @@ import torch
 from torch import Tensor
 
 from ._cabi import call
+from .stepio import zero_counter
 
 _Item = Tuple[object, Callable[[str], BaseException], str]   # (0-d flag tensor | () -> flag tensor, exception type, message)
 _active: Optional[List[_Item]] = None
@@ -88,7 +89,6 @@ def simplex_violations(t: Tensor, axis: int = 1, tol: float = 2e-4) -> Tensor:
     inner = 1
     for d in t.shape[axis + 1:]:
         inner *= d
-    from .ops import zero_counter
     count = zero_counter(t.device)         # inside an iteration: a counter of the step block (zeroed by its upload), else torch.zeros
     if t.numel():
         call("miseg_simplex_violations", torch.cuda.current_stream().cuda_stream, t.data_ptr(), outer, t.shape[axis], inner,

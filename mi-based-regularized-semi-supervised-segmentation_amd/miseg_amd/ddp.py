@@ -20,7 +20,10 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
+from . import unet_ops
+from ._rt import wait_stream
 from .flat import FlatBuffers
+from .tape import host_call
 
 
 def init_from_env(backend: Optional[str] = None) -> bool:
@@ -122,12 +125,11 @@ class GradReducer:
         # others: the backward pass's own stream never waits for the weight gradients to drain in the middle of the pass, and no further
         # stream is created -- with RCCL's own that makes four, the number of hardware queues a process gets by default
         # (GPU_MAX_HW_QUEUES); a fifth stream shares a queue with one of the others and the step time became bimodal (6.95 / 7.4 ms).
-        from . import ops, unet_ops
         dev = self.flat.flat_grad.device
         cur = torch.cuda.current_stream(dev)
         rs = unet_ops.wgrad_stream(dev)
         for s in [cur] + [s for s in self.producer_streams if s != cur and s != rs]:
-            ops.wait_stream(rs, s)
+            wait_stream(rs, s)
         torch.cuda.set_stream(rs)       # (not the `with torch.cuda.stream` context: 15-20 us of host time per use)
         try:
             self.flat.collect(lo, hi)   # joins the weight-gradient stream into rs; gradients autograd parked elsewhere -> flat slice
@@ -141,7 +143,6 @@ class GradReducer:
                 self._handles[b] = dist.all_reduce(self.flat.flat_grad[start:end], op=op, group=self.group, async_op=True)
             finally:
                 torch.cuda.set_stream(back)
-        from .tape import host_call
         host_call(allreduce)
 
     def prepare(self) -> None:
@@ -168,7 +169,6 @@ class GradReducer:
             if self._handles[b] is None:  # some parameter of the bucket got no gradient this step (or its trigger fired early)
                 self._launch(b)
         if self.flat.flat_grad.is_cuda:
-            from .tape import host_call
             host_call(self._wait_all)     # (a replayed launch tape repeats it at this point of the iteration)
         else:
             self._wait_all()

@@ -19,7 +19,10 @@ import torch
 from torch import Tensor
 
 from . import unet_ops
-from .gradslot import grad_slot  # noqa: F401  (re-exported)
+from ._cabi import call
+from ._rt import PinnedRing, _stream, fill_zero
+from .gradslot import adjacent_groups, grad_slot  # noqa: F401  (grad_slot: re-exported)
+from .tape import keep
 
 
 OWNERS: "weakref.WeakValueDictionary[int, FlatBuffers]" = weakref.WeakValueDictionary()   # id(first given parameter) -> its buffers
@@ -90,7 +93,6 @@ class FlatBuffers:
 
     @staticmethod
     def _layout_order(params):
-        from .gradslot import adjacent_groups
         mine = {id(p) for p in params}
         group_of = {}
         for grp in adjacent_groups():
@@ -125,29 +127,24 @@ class FlatBuffers:
         self.ensure()
         hi = len(self.params) if hi is None else hi
         if self.flat_grad.is_cuda:
-            from .unet_ops import join_wgrad_streams
-            join_wgrad_streams()          # weight gradients are written into the slots from a side stream
+            unet_ops.join_wgrad_streams()          # weight gradients are written into the slots from a side stream
         with torch.no_grad():
             for i in range(lo, hi):
                 p, slot = self.params[i], self.slots[i]
                 g = p.grad
                 if g is None:
                     if slot.is_cuda:
-                        from .ops import fill_zero
                         fill_zero(slot)                # library launches: they are on the launch tape
                     else:
                         slot.zero_()
                 elif g.data_ptr() != slot.data_ptr():
                     if slot.is_cuda and g.dtype == slot.dtype and g.shape == slot.shape and g.is_contiguous() and g.data_ptr() % 16 == 0:
-                        from ._cabi import call
-                        from .ops import _stream
                         call("miseg_copy", _stream(), slot.data_ptr(), g.data_ptr(), slot.numel() * 4)   # a kernel, not hipMemcpyDtoD (which can stall for 100s of us on a busy device)
                     elif slot.is_cuda and g.dtype == slot.dtype and g.shape == slot.shape:
                         torch.mul(g, 1.0, out=slot)
                     else:
                         slot.copy_(g)
                     if g.is_cuda:
-                        from .tape import keep
                         keep(g, torch.cuda.current_stream(g.device))   # may be another stream than g's own (GradReducer._launch)
                 else:
                     continue
@@ -347,7 +344,6 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
                 continue
             ring = self._hyper_host[gi]
             if ring is None:
-                from .ops import PinnedRing
                 ring = self._hyper_host[gi] = PinnedRing((self._HYPER_WORDS,), torch.float32, slots=4)
             ring.upload_into(lambda slot: slot.copy_(vals), self._hyper[gi])
 

@@ -15,6 +15,9 @@ from typing import Dict, List, Sequence, Tuple, Union
 import torch
 from torch import Tensor
 
+from . import checks as _checks, stepio
+from ._cabi import call
+
 Number = Union[int, float]
 _CONST: Dict[tuple, Tensor] = {}
 
@@ -88,7 +91,6 @@ class LinearLoss:
         """Seed autograd at the kernel outputs with constant gradients ``coefficient * scale`` (``scale`` = the loss scale of the fp16
         storage mode).  Inside an iteration the constants live in the step block (``stepio.StepIO.seed``: refreshed by the iteration's
         one upload with the CURRENT scale, so a dynamic loss scale needs no new tensors); otherwise cached ``torch.full`` tensors."""
-        from . import stepio
         io = stepio.CURRENT
         roots, grads = [], []
         for t, c in self.merged():
@@ -154,8 +156,6 @@ def report(items: Sequence[Union[LinearLoss, Tensor]], check_items: Sequence[tup
     order -- what ``evaluate(items, passthrough=[flag_tensor(c) ...])`` returns, but on the GPU as (at most) two ``torch.cat`` and
     ONE launch of ``miseg_report_scalars`` instead of ~20 one-element kernels (isfinite / where / two mat-vecs; isnan-sum-cast per
     NaN test; a cast per integer flag).  Falls back to ``evaluate`` off the GPU or for flag kinds the kernel does not know."""
-    from . import checks as _checks
-    from ._cabi import call
     items = [LinearLoss.of(x) for x in items]
     srcs = [c[0] for c in check_items]
     tensors_all = [t for it in items for t, _ in it.terms] + [s.tensor if isinstance(s, _checks.LazyFlag) else s for s in srcs if not callable(s) or isinstance(s, _checks.LazyFlag)]
@@ -166,7 +166,6 @@ def report(items: Sequence[Union[LinearLoss, Tensor]], check_items: Sequence[tup
         return evaluate(items, passthrough=[_checks.flag_tensor(c) for c in check_items])
     dev = tensors_all[0].device
     cur = torch.cuda.current_stream(dev)
-    from . import stepio
     io = stepio.CURRENT
     if io is not None and io.device == dev:
         out = _report_in_place(io, items, srcs, _checks, cur)
@@ -225,7 +224,6 @@ def _report_in_place(io, items, srcs, _checks, cur) -> "Tensor | None":
     (``stepio.StepIO.scalar`` / ``counter``: the loss kernels and the heads wrote them there): the kernel reads the arena in place
     -- no ``torch.cat`` -- and writes into the iteration's read-back block.  One slot is left free behind the flags: the fp16 mode's
     overflow count goes there, so that the optimiser's guard stays one contiguous vector.  None if anything lives elsewhere."""
-    from ._cabi import call
     cols: List[Tuple[int, int]] = []
     for it in items:
         for t, _ in it.terms:

@@ -1,0 +1,172 @@
+"""Pixel-wise losses on the logits (csrc/losses.hip, dice.hip): each is one fused kernel that also leaves the gradient of the
+logits, which the backward only has to scale."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from .. import checks
+from .._cabi import query
+from .._rt import _need_gpu, _ptr, _stream, _ws, empty_nhwc, logits_nhwc
+from ..stepio import scalar_out, zero_counter
+from ._pkg import call
+from .batch import _scaled_grad, _split_part_of       # the shared piece: a loss on a part of a split_rows writes that part's rows
+
+
+class _ScaledGradLoss(torch.autograd.Function):
+    """A loss whose forward saved d loss / d logits (``ctx.part``: the logits' place in a split_rows, if any): the backward scales it
+    by the upstream gradient; no other input has a gradient."""
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (grad,) = ctx.saved_tensors
+        return (_scaled_grad(ctx.part, grad, g),) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
+def _outputs(ctx, raw: Tensor, logits: Tensor, want_grad: bool = True):
+    """What every pixel loss writes, for ``logits = logits_nhwc(raw)``: the loss scalar and the buffer for d loss / d logits, saved for
+    the backward (None without ``want_grad``) beside the logits' place in a split_rows (``ctx.part``)."""
+    ctx.part = _split_part_of(raw, logits)
+    loss = scalar_out((), logits.device)
+    grad = empty_nhwc(*logits.shape, torch.float32, logits.device) if want_grad else None
+    if want_grad:
+        ctx.save_for_backward(grad)
+    return loss, grad
+
+
+def _int64_labels(labels: Tensor, n: int, h: int, w: int) -> Tensor:
+    labels = labels.contiguous().view(n, h, w)
+    return labels if labels.dtype == torch.int64 else labels.long()
+
+
+def _report_bad_labels(name: str, bad: Tensor, classes: int) -> None:
+    """Hand the kernel's bad-label flag to ``checks.require_zero`` (raised now, or at the iteration's fetch inside a deferred block)."""
+    checks.require_zero(bad, AssertionError, f"{name}: a label lies outside [0, {classes}) "
+                                             f"(class2one_hot of the {classes}-class configuration would refuse it)")
+
+
+class _SoftmaxKL(_ScaledGradLoss):
+    @staticmethod
+    def forward(ctx, logits: Tensor, labels: Tensor, flag_box: list):
+        _need_gpu(logits, labels)
+        raw, logits = logits, logits_nhwc(logits)
+        n, c, h, w = logits.shape
+        labels = _int64_labels(labels, n, h, w)
+        loss, glogits = _outputs(ctx, raw, logits)
+        bad = zero_counter(logits.device, (1,))
+        ws = _ws(query("miseg_loss_ws_bytes", n, h, w), logits.device)
+        call("miseg_softmax_kl", _stream(), _ptr(logits), _ptr(labels), n, h, w, c, None, _ptr(loss), _ptr(glogits), _ptr(bad),
+             _ptr(ws), ws.numel())
+        flag_box.append(bad)      # the bad-label flag, handed to softmax_kl beside the graph (a second output would cost the backward a zeros launch)
+        return loss
+
+
+def softmax_kl(logits: Tensor, labels: Tensor, check_labels: bool = True) -> Tensor:
+    """KL_div(softmax(logits), class2one_hot(labels)) with reduction='mean'.  A label outside [0, C) -- an ignore index, a mask with
+    more classes than the configuration -- makes the reference's ``class2one_hot`` raise AssertionError; the kernel flags it (such a
+    pixel adds nothing to the loss and gets a zero gradient) and, with ``check_labels``, the flag goes to ``checks.require_zero``:
+    raised here outside a ``checks.deferred`` block (one host read, as the evaluation epochers do: they read the loss right after
+    anyway), and at the iteration's fetch inside one (the train step: the flag is one of the iteration's int32 counters and travels with
+    its report -- no launch, no synchronisation)."""
+    flag_box: list = []
+    loss = _SoftmaxKL.apply(logits, labels, flag_box)
+    if check_labels:
+        _report_bad_labels("softmax_kl", flag_box[0], int(logits.shape[1]))
+    return loss
+
+
+class _SoftmaxMSE(_ScaledGradLoss):
+    entry = "miseg_softmax_mse"
+
+    @classmethod
+    def forward(cls, ctx, a: Tensor, b: Tensor, flips: Optional[Tensor]):
+        _need_gpu(a, b, flips)
+        raw, a, b = a, logits_nhwc(a), logits_nhwc(b.detach())
+        n, c, h, w = a.shape
+        loss, ga = _outputs(ctx, raw, a)
+        ws = _ws(query("miseg_loss_ws_bytes", n, h, w), a.device)
+        call(cls.entry, _stream(), _ptr(a), _ptr(b), _ptr(flips), n, h, w, c, None, _ptr(loss), _ptr(ga), _ptr(ws), ws.numel())
+        return loss
+
+
+def softmax_mse(a: Tensor, b: Tensor, flips: Optional[Tensor] = None) -> Tensor:
+    """mean((softmax(a) - softmax(flip(b)).detach())**2); ``flips`` replays the per-sample flip on b."""
+    return _SoftmaxMSE.apply(a, b, flips)
+
+
+class _SoftmaxKLCons(_SoftmaxMSE):
+    entry = "miseg_softmax_klcons"
+
+
+def softmax_kl_consistency(a: Tensor, b: Tensor, flips: Optional[Tensor] = None) -> Tensor:
+    """KL_div()(softmax(a), softmax(flip(b)).detach()) -- the `UDARegCriterion.name: kl` consistency term, fused like softmax_mse."""
+    return _SoftmaxKLCons.apply(a, b, flips)
+
+
+_LOSS_CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)     # MISEG_DISPATCH_C of csrc/losses.hip
+
+
+def softmax_entropy_supported(c: int) -> bool:
+    """Whether ``softmax_entropy`` has a kernel for ``c`` classes (the pixel losses' dispatch list: 2-6, 8, 10, 16)."""
+    return int(c) in _LOSS_CLASS_COUNTS
+
+
+class _SoftmaxEntropy(_ScaledGradLoss):
+    @staticmethod
+    def forward(ctx, logits: Tensor):
+        _need_gpu(logits)
+        raw, logits = logits, logits_nhwc(logits)
+        n, c, h, w = logits.shape
+        loss, glogits = _outputs(ctx, raw, logits)
+        ws = _ws(query("miseg_loss_ws_bytes", n, h, w), logits.device)
+        call("miseg_softmax_entropy", _stream(), _ptr(logits), n, h, w, c, None, _ptr(loss), _ptr(glogits), _ptr(ws), ws.numel())
+        return loss
+
+
+def softmax_entropy(logits: Tensor) -> Tensor:
+    """Entropy(reduction='mean', eps=1e-16)(softmax(logits, 1)) = mean_{n,h,w} -sum_c p_c log(p_c + 1e-16), one fused kernel with its
+    backward; a per-sample flip of the logits does not change it.  Class counts: ``softmax_entropy_supported``."""
+    return _SoftmaxEntropy.apply(logits)
+
+
+def softmax_dice_supported(c: int) -> bool:
+    """Whether ``softmax_dice`` has a kernel for ``c`` classes (the pixel losses' dispatch list: 2-6, 8, 10, 16)."""
+    return int(c) in _LOSS_CLASS_COUNTS
+
+
+class _SoftmaxDice(_ScaledGradLoss):
+    @staticmethod
+    def forward(ctx, logits: Tensor, labels: Tensor, flag_box: list, consts: tuple, class_weight: Optional[Tensor], want_grad: bool):
+        _need_gpu(logits, labels, class_weight)
+        raw, logits = logits, logits_nhwc(logits)
+        n, c, h, w = logits.shape
+        labels = _int64_labels(labels, n, h, w)
+        power, eps, kl_weight, dice_weight = consts
+        loss, glogits = _outputs(ctx, raw, logits, want_grad)      # evaluation: forward only, no gradient pass
+        bad = zero_counter(logits.device, (1,))
+        ws = _ws(query("miseg_softmax_dice_ws_bytes", n, h, w, c), logits.device)
+        call("miseg_softmax_dice", _stream(), _ptr(logits), _ptr(labels), n, h, w, c, power, eps, _ptr(class_weight), kl_weight,
+             dice_weight, None, _ptr(loss), _ptr(glogits), _ptr(bad), _ptr(ws), ws.numel())
+        flag_box.append(bad)      # the bad-label flag, handed over beside the graph as in _SoftmaxKL
+        return loss
+
+
+def softmax_dice(logits: Tensor, labels: Tensor, *, pow: int = 1, eps: float = 1e-8, class_weight: Optional[Tensor] = None,
+                 kl_weight: float = 0.0, dice_weight: float = 1.0, check_labels: bool = True) -> Tensor:
+    """``kl_weight * KL_div()(p, t) + dice_weight * GeneralizedDiceLoss(eps, class_weight, pow)(p, t)`` for ``p = softmax(logits, 1)``
+    and ``t = class2one_hot(labels)``, reduction 'mean', in the fused entry point ``miseg_softmax_dice`` with its backward (with
+    ``kl_weight == 0`` the KL part is not computed).  ``class_weight``: a float32 vector of C entries on the logits' device (the
+    criterion objects upload theirs once), or None.  Under ``torch.no_grad()`` the gradient pass is not launched.  A label outside
+    [0, C) is flagged, adds nothing and gets a zero gradient; with ``check_labels`` the flag goes to ``checks.require_zero`` exactly
+    as in ``softmax_kl``.  Class counts: ``softmax_dice_supported``."""
+    if class_weight is not None:
+        assert class_weight.dtype == torch.float32 and class_weight.is_contiguous() and class_weight.numel() == int(logits.shape[1]), \
+            (class_weight.dtype, tuple(class_weight.shape), int(logits.shape[1]))
+    flag_box: list = []
+    want_grad = torch.is_grad_enabled() and logits.requires_grad
+    loss = _SoftmaxDice.apply(logits, labels, flag_box, (int(pow), float(eps), float(kl_weight), float(dice_weight)), class_weight, want_grad)
+    if check_labels:
+        _report_bad_labels("softmax_dice", flag_box[0], int(logits.shape[1]))
+    return loss

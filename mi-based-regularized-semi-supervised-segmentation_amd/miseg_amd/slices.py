@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _cabi
+from ._rt import PinnedRing
 
 JOB_INTS, MAX_GEO = 48, 4
 CROP, VFLIP, HFLIP, AFFINE = 1, 2, 3, 4
@@ -289,7 +290,6 @@ class ResidentSlices:
         # run-ahead x safety): a pageable `.to(device)` is a synchronous copy, i.e. the host would wait for the GPU queue to drain
         # once per batch (semi_seg/epocher.py `_upload_flips` has the measurement)
         jh = torch.from_numpy(np.ascontiguousarray(jobs, dtype=np.int32))
-        from .ops import PinnedRing
         rings = self.__dict__.setdefault("_job_ring", {})
         key = tuple(jh.shape)
         ring = rings.get(key)

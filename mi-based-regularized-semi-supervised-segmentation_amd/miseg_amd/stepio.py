@@ -20,6 +20,7 @@ from torch import Tensor
 
 from . import _cabi
 from ._cabi import call
+from ._rt import _stream
 
 FLIPS_OFF, FLIPS_CAP = 0, 512                 # int32
 HYPER_OFF, HYPER_CAP = 2048, 64               # float32: 8 per parameter group (Adam: lr/bc1, 1/sqrt(bc2), eps, wd, 1/loss scale; words
@@ -44,6 +45,24 @@ def block_bytes(forwards: int) -> int:
 
 def current() -> Optional["StepIO"]:
     return CURRENT
+
+
+def scalar_out(shape, device) -> Tensor:
+    """fp32 tensor for a kernel's small result: inside an iteration it lives in the iteration's scalar arena, where the report kernel
+    reads it in place; otherwise an ordinary allocation."""
+    io = CURRENT
+    if io is not None and io.device == device:
+        return io.scalar(shape)
+    return torch.empty(tuple(shape), dtype=torch.float32, device=device)
+
+
+def zero_counter(device, shape=()) -> Tensor:
+    """int32 counter that is zero before the kernel that adds to it runs: inside an iteration the step block's upload has zeroed it
+    (no fill launch); otherwise torch.zeros."""
+    io = CURRENT
+    if io is not None and io.device == device:
+        return io.counter().view(tuple(shape))
+    return torch.zeros(tuple(shape), dtype=torch.int32, device=device)
 
 
 class Ticket:
@@ -130,7 +149,6 @@ class StepIO:
 
     def upload(self, slot: int) -> None:
         """The one host -> device copy of the iteration (current stream) and the event that frees the slot."""
-        from .ops import _stream
         st = _stream()
         call("miseg_upload", st, self.dev.data_ptr(), self.host[slot].data_ptr(), self.param_bytes)
         call("miseg_event_record", st, self.up_events[slot])
@@ -253,7 +271,6 @@ class StepIO:
         """Enqueue the one download of the block and the event behind it (current stream)."""
         self.out_turn = (self.out_turn + 1) % len(self.out_events)
         slot = self.out_turn
-        from .ops import _stream
         st = _stream()
         nbytes = (self._cursor_out + 15) // 16 * 16
         call("miseg_download", st, self.out_host[slot].data_ptr(), self.out_dev.data_ptr(), nbytes)

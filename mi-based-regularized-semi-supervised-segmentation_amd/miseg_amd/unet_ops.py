@@ -18,11 +18,11 @@ import weakref
 import torch
 from torch import Tensor
 
+from . import _cabi, stepio
 from ._cabi import call, query
+from ._rt import _DT, _GradJoin, _need_gpu, _ptr, _stream, _ws, as_nhwc, empty_nhwc, wait_stream
 from .gradslot import grad_slot
-from .ops import _DT, _need_gpu, _ptr, _stream, _ws, as_nhwc, empty_nhwc, wait_stream
 from .tape import keep
-from . import stepio
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 
@@ -519,8 +519,8 @@ class _ConvBNReLU(torch.autograd.Function):
                 gy[a:b] += g2.to(dtype)
         rec, rec0, rec1 = ctx.recs
         ext_parts, ext_nparts = rec.take(gy) if rec is not None else (None, 0)
-        stem_dgrad = bool(ctx.needs_input_grad[0] and weight.shape[1] < c0)     # the gradient of the image behind a padded stem operand
-        if _FUSE_BN_BWD and not want_pool and gpool is None and gy is not None and not stem_dgrad and _dgrads_fusable(ctx, dtype):
+        stem_grad = bool(ctx.needs_input_grad[0] and weight.shape[1] < c0)     # the gradient of the image behind a padded stem operand
+        if _FUSE_BN_BWD and not want_pool and gpool is None and gy is not None and not stem_grad and _dgrads_fusable(ctx, dtype):
             return _ConvBNReLU._backward_fused(ctx, gy, ext_parts, ext_nparts)
         gy = None if gy is None else as_nhwc(gy.to(dtype))
         gpool = None if gpool is None else as_nhwc(gpool.to(dtype))
@@ -603,7 +603,6 @@ class _ConvBNReLU(torch.autograd.Function):
                      tag=f"conv3x3_wgrad[{h}x{w},{c0 + c1}->{cout}]")
                 if gw_full is not gw:
                     call("miseg_conv3x3_wgrad_slice", stream_handle, _ptr(gw_full), cout, c0 + c1, weight.shape[1], _ptr(gw))
-            from . import _cabi
             if side is None:
                 launch(_stream())
             elif _cabi.TIMER is not None:       # the per-kernel timer records its events on torch's current stream
@@ -612,7 +611,6 @@ class _ConvBNReLU(torch.autograd.Function):
             else:
                 launch(side.cuda_stream)
         grads = [None, None]
-        from .ops import _GradJoin
         if _DUAL_DGRAD and x1 is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not ups0 and not ups1 and \
                 c0 % 16 == 0 and c1 % 4 == 0 and not _GradJoin.enabled and not (_FUSE_BN_BWD and _FUSE_BN_RED) and not _RED_ONLY:
             # concat of two full-resolution sources: both data gradients in ONE launch (graw read once, twice the blocks)
@@ -622,13 +620,12 @@ class _ConvBNReLU(torch.autograd.Function):
                  work=(18.0 * (c0 + c1) * cout * n * h * w, float(raw.element_size()) * n * h * w * (c0 + c1 + cout)),
                  tag=f"conv3x3_dgrad[{h}x{w},{cout}->{c0}+{c1}]")
             return g0, g1, gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
-        if stem_dgrad:
+        if stem_grad:
             cin = weight.shape[1]
             sink = ctx.stem_sink
             if sink is not None and _STEM_DGRAD and cin == 1 and query("miseg_conv3x3_stem_dgrad_supported", _DT[dtype], cout, w):
                 # one image channel: the stem's own kernel writes the fp32 image gradient; it reaches the image through the sink
-                from .ops import stem_dgrad as _stem_dgrad
-                sink.grad = _stem_dgrad(graw, weight)
+                sink.grad = stem_dgrad(graw, weight)
                 return None, None, gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
             # the generic path; the padded channels' gradients are computed and dropped (stem_input's backward keeps the real ones)
             gfull = stem_dgrad_generic(graw, weight, c0)
@@ -640,7 +637,6 @@ class _ConvBNReLU(torch.autograd.Function):
             if ups and _FUSE_UPS_DGRAD and query("miseg_conv3x3_fwd_sumpool_supported", _DT[dtype], cout, n, h, w, cs):
                 # the source was read through the x2 upsample: its gradient is the 2x2 sum-pool of the data gradient -- pooled in the
                 # convolution's epilogue, the full-resolution gradient (4x the bytes) never exists
-                from .ops import _GradJoin
                 joined = _GradJoin.take(xs) if query("miseg_conv3x3_fwd_sumpool_acc_supported", _DT[dtype], cout, n, h, w) else None
                 if joined is not None:
                     # the source is also a local-MI tap and its head's backward has already written its gradient: add ours into it
@@ -761,6 +757,25 @@ class _ConvBNReLU(torch.autograd.Function):
         return grads[0], grads[1], gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
 
 
+def stem_dgrad_supported(dtype, cout: int, w: int) -> bool:
+    """Whether ``stem_dgrad`` has a kernel for this storage type, channel count and row length (``miseg_conv3x3_stem_dgrad_supported``)."""
+    return dtype in _DT and bool(query("miseg_conv3x3_stem_dgrad_supported", _DT[dtype], int(cout), int(w)))
+
+
+def stem_dgrad(graw: Tensor, weight: Tensor) -> Tensor:
+    """Data gradient of the one-channel stem convolution: ``graw`` = NHWC [N,Cout,H,W] of the storage type (the gradient of the raw
+    convolution output), ``weight`` = the fp32 master [Cout,1,3,3] -> fp32 [N,1,H,W] (``miseg_conv3x3_stem_dgrad``)."""
+    _need_gpu(graw, weight)
+    graw = as_nhwc(graw)
+    n, cout, h, w = graw.shape
+    assert weight.dtype == torch.float32 and tuple(weight.shape) == (cout, 1, 3, 3) and weight.is_contiguous(), (weight.shape, weight.dtype)
+    out = torch.empty((n, 1, h, w), dtype=torch.float32, device=graw.device)
+    ws = _ws(query("miseg_conv3x3_stem_dgrad_ws_bytes", cout), graw.device)
+    call("miseg_conv3x3_stem_dgrad", _stream(), _DT[graw.dtype], _ptr(graw), n, h, w, cout, _ptr(weight), _ptr(out), _ptr(ws), ws.numel(),
+         work=(18.0 * cout * n * h * w, float(n * h * w) * (graw.element_size() * cout + 4.0)), tag=f"conv3x3_stem_dgrad[{h}x{w},{cout}->1]")
+    return out
+
+
 def stem_dgrad_generic(graw: Tensor, weight: Tensor, cp: int) -> Tensor:
     """The stem's data gradient without its own kernel: ``weight`` (fp32 [Cout,Cin,3,3], Cin below one channel vector) with its input
     channels zero-padded to ``cp``, packed for the data gradient (kind 1), through the streaming / tiled convolution over ``graw``
@@ -787,7 +802,6 @@ def _second_user_waits(pw, dev) -> None:
 
 def _dgrads_fusable(ctx, dtype) -> bool:
     """Can every data-gradient launch of this layer's backward form graw in its loader?"""
-    from .ops import _GradJoin
     training, ups0, ups1, want_pool, c0, c1, n, h, w, cout = ctx.cfg
     if _GradJoin.enabled or cout % vec_of(dtype):
         return False
@@ -834,7 +848,6 @@ class _Conv1x1(torch.autograd.Function):
         bf = bias.contiguous().float()
         out = empty_nhwc(n, cout, h, w, torch.float32, x.device)
         call("miseg_conv1x1_fwd", _stream(), _DT[x.dtype], _ptr(x), n, h, w, cin, _ptr(wf), _ptr(bf), cout, _ptr(out))
-        from .ops import _GradJoin
         _GradJoin.clear()                # offers of an earlier backward pass that nobody took
         ctx.save_for_backward(x, wf)
         ctx.wshape = tuple(weight.shape)
@@ -860,7 +873,6 @@ class _Conv1x1(torch.autograd.Function):
         call("miseg_conv1x1_bwd", _stream(), _DT[x.dtype], _ptr(x), _ptr(gout), n, h, w, cin, _ptr(wf), cout, _ptr(gin), _ptr(gw), _ptr(gb),
              _ptr(ws), ws.numel())
         if gin is not None:
-            from .ops import _GradJoin
             _GradJoin.offer(x, gin)      # a tap's head backward may add its gradient of x into this tensor (ops._GradJoin)
         return gin, gw.view(ctx.wshape) if want_w else None, gb if want_b else None
 
