@@ -157,6 +157,22 @@ int miseg_iic_local_bwd(void* stream, const float* x, const float* y, const floa
                         const float* grad_raw, const float* scale, float* gx, float* gy, int accumulate, int precision,
                         void* ws, int64_t ws_bytes);
 int64_t miseg_iic_local_bwd_ws_bytes(int64_t K, int64_t pad, int64_t P);
+/* Which kernel variant miseg_iic_local_joint_fwd (exact fp32 path) and miseg_iic_local_bwd launch for a shape: pure host queries on the
+ * functions the two entry points themselves decide by (plan_joint / plan_bwd, csrc/mi_local.h); no stream, no launch.  -1: refused.
+ * joint_plan : bits 0-7   cap  = 4 | 9: joint_fwd_kernel<cap, cap>, tiles of 16 rows of D = T*K per dimension one block holds
+ *              bits 8-15  sb   = sub-blocks per dimension of D (the grid's y holds P * sb * sb slots)
+ *              bits 16-23 tps  = 16-row tiles per sub-block
+ *              bits 24-31 RB, bits 32-39 WB = rows / columns of the staged image tile (8x64, 4x64, 4x32, 4x16)
+ *              bits 40-55 G    = persistent blocks per slot (a block walks items G apart)
+ * bwd_plan   : bits 0-3   kind = 1 rows (the 16-bit matrix-core kernels), 2 local_bwd2_kernel, 3 local_bwd_kernel (direct form)
+ *              bits 4-7   width: rows -- products per fp32-class product (1 bf16, 3 bf16x3, 2 f16 + fp8); bwd2 -- MT = 4 | 9;
+ *                         direct -- NTP = 4 | 2 | 1 pixel tiles of 16
+ *              bit  8     gInLds (direct: the gradient matrix is staged in LDS; bwd2: always 1; rows: 0)
+ *              bit  9     plain_rmw (bwd2: col2im by plain LDS read-modify-write, else LDS atomics)
+ *              bits 16-23 WB = output columns per item (bwd2: 64 - 2 pad, direct: 16 NTP, rows: 64)
+ *              masked = whether a mask is passed, precision as above (both select the rows kernels). */
+int64_t miseg_iic_local_joint_plan(int64_t N, int64_t K, int64_t H, int64_t W, int64_t pad, int64_t P);
+int64_t miseg_iic_local_bwd_plan(int64_t N, int64_t K, int64_t H, int64_t W, int64_t pad, int64_t P, int masked, int precision);
 /* The same local MI on the NETWORK OUTPUT (the `midl` trainer): x = softmax(flip(b)), y = softmax(a) computed
  * in registers from fp32 NHWC logits a, b [N][H][W][C] (the rows miseg_softmax_mse reads; flips = its int32[N] mask applied to b),
  * never written out.  2 <= C <= 8 and 0 <= pad <= 3; anything else returns MISEG_E_INVALID ("unsupported configuration"), and the

@@ -113,6 +113,47 @@ static inline MiPlanes mi_planes(unsigned char* base, int64_t maps, int64_t HW) 
 }
 int launch_make_planes(hipStream_t st, const float* probs, int64_t maps, int64_t HW, unsigned char* planes);
 size_t local_bwd_f8_ws_bytes(int64_t K, int64_t pad, int64_t P);
+
+// Which kernel miseg_iic_local_bwd launches, from the shape alone (miseg_iic_local_bwd_plan reports exactly this):
+//   kRows   -- the 16-bit matrix-core kernels (precision != 0, no mask, K = 20, pad 1 | 3); width = products per fp32-class product
+//   kBwd2   -- local_bwd2_kernel<width> (width = 4 | 9 tiles of 16 rows of (b, o)), WB = 64 - 2 pad useful columns per tile
+//   kDirect -- local_bwd_kernel<width> (width = 4 | 2 | 1 pixel tiles of 16, WB = 16 width), G in LDS or read from global memory
+struct BwdPlan {
+    enum Kind { kRows = 1, kBwd2 = 2, kDirect = 3 };
+    int kind, width, gInLds, plain_rmw, WB;
+    size_t lds;              // dynamic LDS of the kernel (kBwd2, kDirect)
+};
+static inline int nterms_of(int precision) { return precision == 1 ? 3 : precision == 3 ? 2 : 1; }   // precision (miseg_hip.h) -> products
+static inline bool plan_bwd(BwdPlan& b, int64_t N, int64_t K, int64_t H, int64_t W, int64_t pad, int64_t P, bool masked, int precision) {
+    if (N <= 0 || K <= 0 || K > 32 || H <= 0 || W <= 0 || pad < 0 || P <= 0) return false;
+    b.kind = 0; b.width = 0; b.gInLds = 0; b.plain_rmw = 0; b.WB = 0; b.lds = 0;
+    if (precision != 0 && !masked && local_bwd_bf16_supported(N, K, H, W, pad)) {   // bf16 MFMA, hi/lo split (1) or plain (2); f16 + fp8 (3)
+        b.kind = BwdPlan::kRows; b.WB = 64;
+        b.width = nterms_of(precision);
+        if (b.width == 2 && !local_bwd_f8_supported(K, pad)) b.width = 3;
+        return true;
+    }
+    const int k = (int)K, Kc = (k + 3) & ~3, p = (int)pad, T = 2 * p + 1, RS = 4 + 2 * p;
+    {   // fast path: transposed GEMM + LDS col2im (needs T*K <= 144 rows and the G matrix + tiles in LDS)
+        const int Mdim = T * k, Kred = T * Kc, WB = 64 - 2 * p, planeS = (RS * 64) | 1, gstride = Kred | 1;
+        const int mt = (Mdim + 15) / 16, mtc = mt <= 4 ? 4 : 9;
+        const size_t lds2 = ((size_t)mtc * 16 * gstride + (size_t)Kc * planeS + (size_t)4 * k * 68 + (size_t)mtc * 16) * 4;
+        if (mt <= 9 && WB >= 16 && RS <= 10 && Kc <= 20 && lds2 <= (size_t)kLdsBudget) {
+            b.kind = BwdPlan::kBwd2; b.width = mtc; b.WB = WB; b.lds = lds2; b.gInLds = 1;
+            b.plain_rmw = (4 % k != 0) && (8 % k != 0) && (12 % k != 0);
+            return true;
+        }
+    }
+    b.kind = BwdPlan::kDirect;
+    for (int inLds = 1; inLds >= 0 && !b.width; --inLds)
+        for (int cand : {4, 2, 1}) {
+            const int WS = 16 * cand + 2 * p, planeS = (RS * WS) | 1;
+            const size_t srcb = (size_t)Kc * planeS * 4, gb = inLds ? (size_t)T * T * Kc * k * 4 : 0;
+            if (srcb + gb <= (size_t)kLdsBudget) { b.gInLds = inLds; b.width = cand; b.WB = 16 * cand; b.lds = srcb + gb; break; }
+        }
+    return b.width != 0;
+}
+
 int launch_local_bwd_f8(hipStream_t st, const float* x, const float* y, int64_t S, int64_t hs, int64_t N, int64_t K, int64_t H, int64_t W,
                         int64_t pad, const int32_t* win, int64_t P, const float* grad_raw, const float* scale, float* gx, float* gy,
                         int accumulate, void* ws, const unsigned char* planes);

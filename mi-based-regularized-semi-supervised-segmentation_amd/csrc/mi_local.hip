@@ -296,13 +296,16 @@ __global__ __launch_bounds__(1024) void local_loss_disp_kernel(const float* __re
 __global__ __launch_bounds__(64) void local_loss_finish_kernel(const float* __restrict__ parts, int TT, float* __restrict__ loss) {
     const float* p = parts + (size_t)blockIdx.x * TT;
     const int lane = threadIdx.x;
-    float tot = 0.f;
+    // The terms are of one sign and O(1) each: a serial fp32 sum of the 169 / 225 of pad 6 / 7 rounds every addition at the magnitude of
+    // the running total and lost ~3 bits of the mean (4.9e-7 of a loss of -0.99 at K = 58, pad 7; tests/test_gpu_mi_local_variants.py).
+    // The total is kept in double: 64 lanes, one add per term, still in d order.
+    double tot = 0.0;
     for (int d0 = 0; d0 < TT; d0 += 64) {   // one coalesced load per 64 terms, then the d-ordered sum out of registers
         const float v = d0 + lane < TT ? p[d0 + lane] : 0.f;
         const int m = min(64, TT - d0);
-        for (int d = 0; d < m; ++d) tot += __shfl(v, d, 64);
+        for (int d = 0; d < m; ++d) tot += (double)__shfl(v, d, 64);
     }
-    if (lane == 0) loss[blockIdx.x] = tot / (float)TT;
+    if (lane == 0) loss[blockIdx.x] = (float)(tot / (double)TT);
 }
 
 // -------------------------------------------------------------------------------------------
@@ -640,10 +643,22 @@ __global__ __launch_bounds__(kThreads, 1) void local_bwd2_kernel(const float* __
 
 using namespace miseg;
 
-// precision (include/miseg_hip.h) -> products per fp32-class product: 1 = bf16x3, 2 = plain bf16, 3 = f16 + fp8 cross terms
-static inline int nterms_of(int precision) { return precision == 1 ? 3 : precision == 3 ? 2 : 1; }
-
 extern "C" int64_t miseg_iic_local_planes_bytes(int64_t S, int64_t UB, int64_t K, int64_t H, int64_t W, int64_t pad);
+
+// ---- the dispatch, as numbers (bit layouts: include/miseg_hip.h).  Pure host arithmetic on plan_joint / plan_bwd, the functions the
+// entry points below decide by: no stream, no launch, nothing on the tape.
+extern "C" int64_t miseg_iic_local_joint_plan(int64_t N, int64_t K, int64_t H, int64_t W, int64_t pad, int64_t P) {
+    JointGeom g;
+    if (N <= 0 || K <= 0 || H <= 0 || W <= 0 || P <= 0 || pad < 0 || !plan_joint(g, N, K, H, W, pad, P)) return -1;
+    const int64_t cap = g.tilesM <= 4 ? 4 : 9;
+    return cap | ((int64_t)g.sb << 8) | ((int64_t)g.tps << 16) | ((int64_t)g.RB << 24) | ((int64_t)g.WB << 32) | ((int64_t)g.G << 40);
+}
+
+extern "C" int64_t miseg_iic_local_bwd_plan(int64_t N, int64_t K, int64_t H, int64_t W, int64_t pad, int64_t P, int masked, int precision) {
+    BwdPlan b;
+    if (!plan_bwd(b, N, K, H, W, pad, P, masked != 0, precision)) return -1;
+    return (int64_t)b.kind | ((int64_t)b.width << 4) | ((int64_t)b.gInLds << 8) | ((int64_t)b.plain_rmw << 9) | ((int64_t)b.WB << 16);
+}
 
 extern "C" int64_t miseg_iic_local_joint_ws_bytes(int64_t N, int64_t K, int64_t H, int64_t W, int64_t pad, int64_t P) {
     JointGeom g;
@@ -747,7 +762,8 @@ extern "C" int miseg_iic_local_bwd_heads(void* stream, const float* probs, int64
     MISEG_REQUIRE(probs && win && grad_raw && scale && gprob, "iic_local_bwd_heads: null pointer");
     MISEG_REQUIRE(S > 0 && UB > 0 && K > 0 && K <= 32 && H > 0 && W > 0 && pad >= 0 && P > 0, "iic_local_bwd_heads: bad shape (K<=32)");
     const int64_t hs = 2 * UB * K * H * W, half = UB * K * H * W, TT = (2 * pad + 1) * (2 * pad + 1);
-    if (precision != 0 && local_bwd_bf16_supported(UB, K, H, W, pad)) {
+    BwdPlan bp;
+    if (plan_bwd(bp, UB, K, H, W, pad, P, false, precision) && bp.kind == BwdPlan::kRows) {   // all sub-heads in one launch
         MISEG_REQUIRE(ws && ws_bytes >= (int64_t)local_bwd_bf16_ws_bytes(K, pad, P * S), "iic_local_bwd_heads: workspace too small");
         launch_local_bwd_rows(as_stream(stream), probs, probs + half, S, hs, UB, K, H, W, pad, win, P, grad_raw, scale, gprob, gprob + half,
                               accumulate, ws, nterms_of(precision));
@@ -844,34 +860,32 @@ extern "C" int miseg_iic_local_bwd(void* stream, const float* x, const float* y,
     MISEG_REQUIRE(x && y && win && grad_raw && scale && gx && gy, "iic_local_bwd: null pointer");
     MISEG_REQUIRE(N > 0 && K > 0 && K <= 32 && H > 0 && W > 0 && pad >= 0 && P > 0, "iic_local_bwd: bad shape (K<=32)");
     hipStream_t st = as_stream(stream);
-    if (precision != 0 && mask == nullptr && local_bwd_bf16_supported(N, K, H, W, pad)) {   // bf16 MFMA, hi/lo split (1) or plain (2)
+    BwdPlan bp;   // the one decision (mi_local.h); miseg_iic_local_bwd_plan reports it
+    MISEG_REQUIRE(plan_bwd(bp, N, K, H, W, pad, P, mask != nullptr, precision), "iic_local_bwd: K=%ld pad=%ld does not fit LDS", (long)K, (long)pad);
+    if (bp.kind == BwdPlan::kRows) {   // bf16 MFMA, hi/lo split (1) or plain (2)
         MISEG_REQUIRE(ws && ws_bytes >= (int64_t)local_bwd_bf16_ws_bytes(K, pad, P), "iic_local_bwd: workspace too small for the bf16 path");
         launch_local_bwd_rows(st, x, y, 1, 0, N, K, H, W, pad, win, P, grad_raw, scale, gx, gy, accumulate, ws, nterms_of(precision));
         MISEG_LAUNCH_CHECK("local_bwd_rows_kernel");
         return MISEG_OK;
     }
-    {   // fast path: transposed GEMM + LDS col2im (needs T*K <= 144 rows and the G matrix + tiles in LDS)
+    if (bp.kind == BwdPlan::kBwd2) {   // fast path: transposed GEMM + LDS col2im
         Bwd2Geom b2;
         b2.N = (int)N; b2.K = (int)K; b2.Kc = ((int)K + 3) & ~3; b2.H = (int)H; b2.W = (int)W; b2.pad = (int)pad; b2.T = 2 * (int)pad + 1;
         b2.P = (int)P; b2.Mdim = b2.T * b2.K; b2.Kred = b2.T * b2.Kc; b2.ksteps = b2.Kred / 4;
-        b2.WB = 64 - 2 * b2.pad; b2.RS = 4 + 2 * b2.pad; b2.planeS = (b2.RS * 64) | 1; b2.gstride = b2.Kred | 1; b2.G = 256;
+        b2.WB = bp.WB; b2.RS = 4 + 2 * b2.pad; b2.planeS = (b2.RS * 64) | 1; b2.gstride = b2.Kred | 1; b2.G = 256;
         b2.ablate = 0;
-        const int mt = (b2.Mdim + 15) / 16;
-        const int mtc = mt <= 4 ? 4 : 9;
-        const size_t lds2 = ((size_t)mtc * 16 * b2.gstride + (size_t)b2.Kc * b2.planeS + (size_t)4 * b2.K * 68 + (size_t)mtc * 16) * 4;
+        const size_t lds2 = bp.lds;
         b2.accumulate = accumulate;
-        b2.plain_rmw = (4 % b2.K != 0) && (8 % b2.K != 0) && (12 % b2.K != 0);
-        if (mt <= 9 && b2.WB >= 16 && b2.RS <= 10 && b2.Kc <= 20 && lds2 <= (size_t)kLdsBudget) {
-            if (mtc == 4) {
-                hipFuncSetAttribute((const void*)local_bwd2_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-                hipLaunchKernelGGL((local_bwd2_kernel<4>), dim3(b2.G), dim3(kThreads), lds2, st, x, y, mask, b2, win, grad_raw, scale, gx, gy);
-            } else {
-                hipFuncSetAttribute((const void*)local_bwd2_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-                hipLaunchKernelGGL((local_bwd2_kernel<9>), dim3(b2.G), dim3(kThreads), lds2, st, x, y, mask, b2, win, grad_raw, scale, gx, gy);
-            }
-            MISEG_LAUNCH_CHECK("local_bwd2_kernel");
-            return MISEG_OK;
+        b2.plain_rmw = bp.plain_rmw;
+        if (bp.width == 4) {
+            hipFuncSetAttribute((const void*)local_bwd2_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+            hipLaunchKernelGGL((local_bwd2_kernel<4>), dim3(b2.G), dim3(kThreads), lds2, st, x, y, mask, b2, win, grad_raw, scale, gx, gy);
+        } else {
+            hipFuncSetAttribute((const void*)local_bwd2_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+            hipLaunchKernelGGL((local_bwd2_kernel<9>), dim3(b2.G), dim3(kThreads), lds2, st, x, y, mask, b2, win, grad_raw, scale, gx, gy);
         }
+        MISEG_LAUNCH_CHECK("local_bwd2_kernel");
+        return MISEG_OK;
     }
     if (!accumulate) {  // the direct-form fallback below always accumulates
         hipMemsetAsync(gx, 0, (size_t)N * K * H * W * sizeof(float), st);
@@ -880,21 +894,9 @@ extern "C" int miseg_iic_local_bwd(void* stream, const float* x, const float* y,
     BwdGeom g;
     g.N = (int)N; g.K = (int)K; g.Kc = ((int)K + 3) & ~3; g.H = (int)H; g.W = (int)W; g.pad = (int)pad; g.T = 2 * (int)pad + 1;
     g.P = (int)P; g.RS = 4 + 2 * g.pad;
-    int ntp = 0;
-    size_t ldsb = 0;
-    for (int cand : {4, 2, 1}) {
-        g.WB = 16 * cand; g.WS = g.WB + 2 * g.pad; g.planeS = (g.RS * g.WS) | 1;
-        size_t srcb = (size_t)g.Kc * g.planeS * 4, gb = (size_t)g.T * g.T * g.Kc * g.K * 4;
-        if (srcb + gb <= (size_t)kLdsBudget) { g.gInLds = 1; ntp = cand; ldsb = srcb + gb; break; }
-    }
-    if (!ntp) {
-        for (int cand : {4, 2, 1}) {
-            g.WB = 16 * cand; g.WS = g.WB + 2 * g.pad; g.planeS = (g.RS * g.WS) | 1;
-            size_t srcb = (size_t)g.Kc * g.planeS * 4;
-            if (srcb <= (size_t)kLdsBudget) { g.gInLds = 0; ntp = cand; ldsb = srcb; break; }
-        }
-    }
-    MISEG_REQUIRE(ntp, "iic_local_bwd: K=%ld pad=%ld does not fit LDS", (long)K, (long)pad);
+    const int ntp = bp.width;
+    const size_t ldsb = bp.lds;
+    g.WB = bp.WB; g.WS = g.WB + 2 * g.pad; g.planeS = (g.RS * g.WS) | 1; g.gInLds = bp.gInLds;
     g.G = 256;
 #define MISEG_BWD_LAUNCH(NTP)                                                                                         \
     hipFuncSetAttribute((const void*)local_bwd_kernel<NTP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);   \
