@@ -4,15 +4,14 @@ and a float64 closed form, its ``ValueError``s, the projection head's key layout
 built on the CPU."""
 import os
 import re
-import subprocess
 
 import pytest
 import torch
 
+import trainer_harness as th
 from contrast_ref import closed_form, embeddings as _embeddings
+from trainer_harness import PKG
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
 SHIPPED = {"group_option": "partition", "extract_position": "Conv5", "ptype": "mlp", "output_dim": 256, "temperature": 0.07,
            "base_temperature": 0.07}
 
@@ -191,14 +190,10 @@ def test_supcon_supported_mirrors_the_kernels_range():
 
 def test_library_exports_and_header_declares_the_new_entry_points():
     from miseg_amd import _cabi
-    header = open(os.path.join(ROOT, "include", "miseg_hip.h")).read()
-    lib = os.path.join(PKG, "lib", "libmiseg_hip.so")
-    assert os.path.exists(lib), "build() makes the library"
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    for name, nargs in (("miseg_supcon", 13), ("miseg_supcon_ws_bytes", 2), ("miseg_avgpool_fwd", 8), ("miseg_avgpool_bwd", 8)):
-        assert re.search(r"\b(int|int64_t)\s+" + name + r"\s*\(", header)
-        assert name in _cabi.declared_symbols() and len(_cabi.PROTOTYPES[name][1]) == nargs
-        assert re.search(r"\bT " + name + r"$", out, re.M)
+    new = {"miseg_supcon": 13, "miseg_supcon_ws_bytes": 2, "miseg_avgpool_fwd": 8, "miseg_avgpool_bwd": 8}
+    _, out = th.assert_entry_points(new)
+    for name, nargs in new.items():
+        assert len(_cabi.PROTOTYPES[name][1]) == nargs
     for name in ("f16_miseg_avgpool_fwd", "f16_miseg_avgpool_bwd"):                       # the IEEE-half twins of the pool
         assert re.search(r"\bT " + name + r"$", out, re.M)
     assert _cabi.lib().miseg_version() >= 408

@@ -3,31 +3,12 @@ reads (CLI override included), the epocher it builds, the library's new entry po
 ``Entropy.supports_fused``."""
 import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
+import trainer_harness as th
+from trainer_harness import PKG, ROOT
+
 NEW = "miseg_softmax_entropy"
 DISPATCH = (2, 3, 4, 5, 6, 8, 10, 16)          # MISEG_DISPATCH_C of csrc/losses.hip
-
-
-def _config(argv=()):
-    from deepclustering2.configparser import ConfigManger
-    return ConfigManger(os.path.join(PKG, "config", "semi.yaml"), verbose=False, argv=list(argv))
-
-
-def _trainer(cfg):
-    from contrastyou.arch import UNet
-    from deepclustering2.loss import KL_div
-    from semi_seg.trainer import trainer_zoos
-    tr = trainer_zoos["entmin"].__new__(trainer_zoos["entmin"])
-    tr._config = cfg
-    tr._model = UNet(**cfg["Arch"])
-    tr._init()
-    # what _make_epocher reads besides the section
-    tr._optimizer, tr._labeled_loader, tr._unlabeled_loader, tr._sup_criterion = None, iter(()), iter(()), KL_div(verbose=False)
-    tr._num_batches, tr._cur_epoch, tr._device = 1, 0, "cpu"
-    return tr
 
 
 def test_trainer_zoo_has_entmin_reading_its_section():
@@ -38,7 +19,7 @@ def test_trainer_zoo_has_entmin_reading_its_section():
     assert {"partial", "uda", "iic", "udaiic", "meanteacher", "midl"} <= set(trainer_zoos)
     cfg = yaml.safe_load(open(os.path.join(PKG, "config", "semi.yaml")))
     assert cfg["EntropyMinParameters"] == {"weight": 0.00001}          # the shipped default stays
-    tr = _trainer(cfg)
+    tr = th.bare_trainer("entmin", cfg)
     assert tr._reg_weight == cfg["EntropyMinParameters"]["weight"] == 1e-5
     ep = tr._make_epocher()
     assert type(ep) is E.EntropyMinEpocher and issubclass(E.EntropyMinEpocher, E.TrainEpocher)
@@ -51,23 +32,17 @@ def test_trainer_zoo_has_entmin_reading_its_section():
 
 
 def test_cli_override_reaches_the_epocher():
-    cfg = _config(["Trainer.name=entmin", "EntropyMinParameters.weight=0.5"]).config
-    tr = _trainer(cfg)
+    tr = th.bare_trainer("entmin", th.semi_config(["Trainer.name=entmin", "EntropyMinParameters.weight=0.5"]))
     assert tr._reg_weight == 0.5
     assert tr._make_epocher()._reg_weight == 0.5
 
 
 def test_library_exports_and_header_declares_the_new_entry_point():
     from miseg_amd import _cabi
-    header = open(os.path.join(ROOT, "include", "miseg_hip.h")).read()
+    header, _ = th.assert_entry_points([NEW])
     assert re.search(r"\bint\s+" + NEW + r"\s*\(", header)
-    assert NEW in _cabi.declared_symbols()
     restype, argtypes = _cabi.PROTOTYPES[NEW]
     assert len(argtypes) == 11                     # stream, logits, N, H, W, C, upstream, loss, glogits, ws, ws_bytes
-    lib = os.path.join(PKG, "lib", "libmiseg_hip.so")
-    assert os.path.exists(lib), "build() makes the library"
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"\bT " + NEW + r"$", out, re.M)
 
 
 def test_supported_class_counts_mirror_the_dispatch_list():

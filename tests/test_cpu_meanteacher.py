@@ -2,12 +2,12 @@
 and state, the library's new entry points."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
+import trainer_harness as th
+from trainer_harness import PKG
+
 NEW = ("miseg_ema_update", "miseg_cat_flipped")
 
 
@@ -48,16 +48,9 @@ def test_ema_updater_schedule_and_state_round_trip(golden):
 
 
 def test_library_exports_and_header_declares_the_new_entry_points():
-    from miseg_amd import _cabi
-    header = open(os.path.join(ROOT, "include", "miseg_hip.h")).read()
+    header, _ = th.assert_entry_points(NEW)
     for name in NEW:
         assert re.search(r"\bint\s+" + name + r"\s*\(", header), name
-        assert name in _cabi.declared_symbols()
-    lib = os.path.join(PKG, "lib", "libmiseg_hip.so")
-    assert os.path.exists(lib), "build() makes the library"
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    for name in NEW:
-        assert re.search(r"\bT " + name + r"$", out, re.M), name
 
 
 def test_step_block_sizes():

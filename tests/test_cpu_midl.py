@@ -1,27 +1,11 @@
 """CPU side of the `midl` trainer (``Trainer.name=midl``, the ``MIDLPaperParameters`` section): registration, the sections it reads
 (CLI overrides included), its criterion's patch and step sizes, and the library's new entry points."""
 import os
-import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
+import trainer_harness as th
+from trainer_harness import PKG, ROOT
+
 NEW = ("miseg_iic_out_joint_fwd", "miseg_iic_out_bwd")
-
-
-def _config(argv=()):
-    from deepclustering2.configparser import ConfigManger
-    return ConfigManger(os.path.join(PKG, "config", "semi.yaml"), verbose=False, argv=list(argv))
-
-
-def _trainer(cfg):
-    from contrastyou.arch import UNet
-    from semi_seg.trainer import trainer_zoos
-    tr = trainer_zoos["midl"].__new__(trainer_zoos["midl"])
-    tr._config = cfg
-    tr._model = UNet(**cfg["Arch"])
-    tr._init()
-    return tr
 
 
 def test_trainer_zoo_has_midl_reading_its_sections():
@@ -32,7 +16,7 @@ def test_trainer_zoo_has_midl_reading_its_sections():
     assert {"partial", "uda", "iic", "udaiic", "meanteacher"} <= set(trainer_zoos)
     cfg = yaml.safe_load(open(os.path.join(PKG, "config", "semi.yaml")))
     assert cfg["MIDLPaperParameters"] == {"iic_weight": 0.1, "padding": 1, "patch_size": 1024}
-    tr = _trainer(cfg)
+    tr = th.bare_trainer("midl", cfg)
     assert isinstance(tr._reg_criterion, __import__("torch").nn.MSELoss)
     assert tr._uda_weight == 5.0 and tr._reg_weight == 1.0 and tr._iic_weight == 0.1
     assert (tr._mi_padding, tr._mi_patch_size) == (1, 1024)
@@ -46,9 +30,9 @@ def test_trainer_zoo_has_midl_reading_its_sections():
 
 
 def test_cli_overrides_reach_the_trainer():
-    cfg = _config(["Trainer.name=midl", "MIDLPaperParameters.padding=3", "MIDLPaperParameters.patch_size=32",
-                   "MIDLPaperParameters.iic_weight=0.5", "UDARegCriterion.name=kl", "UDARegCriterion.weight=2.0"]).config
-    tr = _trainer(cfg)
+    cfg = th.semi_config(["Trainer.name=midl", "MIDLPaperParameters.padding=3", "MIDLPaperParameters.patch_size=32",
+                          "MIDLPaperParameters.iic_weight=0.5", "UDARegCriterion.name=kl", "UDARegCriterion.weight=2.0"])
+    tr = th.bare_trainer("midl", cfg)
     from deepclustering2.loss import KL_div
     assert isinstance(tr._reg_criterion, KL_div) and tr._uda_weight == 2.0 and tr._iic_weight == 0.5
     crit = tr.mi_criterion()
@@ -73,16 +57,7 @@ def test_epocher_windows_follow_the_reference_patch_generator():
 
 
 def test_library_exports_and_header_declares_the_new_entry_points():
-    from miseg_amd import _cabi
-    header = open(os.path.join(ROOT, "include", "miseg_hip.h")).read()
-    for name in NEW + ("miseg_iic_out_joint_ws_bytes",):
-        assert re.search(r"\b(int|int64_t)\s+" + name + r"\s*\(", header), name
-        assert name in _cabi.declared_symbols()
-    lib = os.path.join(PKG, "lib", "libmiseg_hip.so")
-    assert os.path.exists(lib), "build() makes the library"
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    for name in NEW + ("miseg_iic_out_joint_ws_bytes",):
-        assert re.search(r"\bT " + name + r"$", out, re.M), name
+    th.assert_entry_points(NEW + ("miseg_iic_out_joint_ws_bytes",))
 
 
 def test_envelope_query():

@@ -9,24 +9,21 @@ import sys
 
 import pytest
 
+import trainer_harness as th
+from trainer_harness import PKG, ROOT
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
 
 
 @pytest.mark.parametrize("name,dtype", [("partial", "bfloat16"), ("uda", "bfloat16"), ("iic", "bfloat16"), ("udaiic", "bfloat16"),
                                         ("udaiic", "float16")])
 def test_main_cli_runs_every_trainer(name, dtype):
     save = f"pytest_cli_{name}_{dtype}"
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    run_dir = th.run_dir(save)
     shutil.rmtree(run_dir, ignore_errors=True)
     try:
-        res = subprocess.run(
-            [sys.executable, "semi_seg/main.py", f"Trainer.name={name}", f"Trainer.save_dir={save}", "Trainer.device=cuda",
-             "Trainer.max_epoch=2", "Trainer.num_batches=3", "Data.size=64", "LabeledData.batch_size=2",
-             "UnlabeledData.batch_size=2", f"Arch.compute_dtype={dtype}"],
-            cwd=PKG, capture_output=True, text=True, timeout=600)
-        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        th.run_main([f"Trainer.name={name}", f"Trainer.save_dir={save}", "Trainer.device=cuda", "Trainer.max_epoch=2", "Trainer.num_batches=3",
+                     "Data.size=64", "LabeledData.batch_size=2", "UnlabeledData.batch_size=2", f"Arch.compute_dtype={dtype}"])
         files = set(os.listdir(run_dir))
         assert {"config.yaml", "last.pth"} <= files, files
     finally:
@@ -39,21 +36,18 @@ def test_main_cli_non_default_iic_configuration():
     paddings 2 / 1 / 3, 32-pixel patches (overlapping windows), the `kl` consistency criterion -- two tiny epochs must run and
     produce finite meters (ref config/semi.yaml:40-63, semi_seg/trainer.py:137-160)."""
     save = "pytest_cli_variants"
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    run_dir = th.run_dir(save)
     shutil.rmtree(run_dir, ignore_errors=True)
     try:
-        res = subprocess.run(
-            [sys.executable, "semi_seg/main.py", "Trainer.name=udaiic", f"Trainer.save_dir={save}", "Trainer.device=cuda",
-             "Trainer.max_epoch=2", "Trainer.num_batches=2", "Data.size=64", "LabeledData.batch_size=2", "UnlabeledData.batch_size=3",
-             "Arch.compute_dtype=bfloat16", "Trainer.feature_names=[Conv5,Up_conv4,Up_conv3,Up_conv2]",
-             "Trainer.feature_importance=[1,0.5,0.5,0.25]", "UDARegCriterion.name=kl",
-             "IICRegParameters.EncoderParams.head_types=mlp", "IICRegParameters.EncoderParams.normalize=true",
-             "IICRegParameters.EncoderParams.num_clusters=10", "IICRegParameters.EncoderParams.num_subheads=3",
-             "IICRegParameters.DecoderParams.head_types=mlp", "IICRegParameters.DecoderParams.normalize=true",
-             "IICRegParameters.DecoderParams.num_clusters=10", "IICRegParameters.DecoderParams.num_subheads=3",
-             "IICRegParameters.LossParams.paddings=[2,1,3]", "IICRegParameters.LossParams.patch_sizes=32"],
-            cwd=PKG, capture_output=True, text=True, timeout=600)
-        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        th.run_main(["Trainer.name=udaiic", f"Trainer.save_dir={save}", "Trainer.device=cuda",
+                     "Trainer.max_epoch=2", "Trainer.num_batches=2", "Data.size=64", "LabeledData.batch_size=2", "UnlabeledData.batch_size=3",
+                     "Arch.compute_dtype=bfloat16", "Trainer.feature_names=[Conv5,Up_conv4,Up_conv3,Up_conv2]",
+                     "Trainer.feature_importance=[1,0.5,0.5,0.25]", "UDARegCriterion.name=kl",
+                     "IICRegParameters.EncoderParams.head_types=mlp", "IICRegParameters.EncoderParams.normalize=true",
+                     "IICRegParameters.EncoderParams.num_clusters=10", "IICRegParameters.EncoderParams.num_subheads=3",
+                     "IICRegParameters.DecoderParams.head_types=mlp", "IICRegParameters.DecoderParams.normalize=true",
+                     "IICRegParameters.DecoderParams.num_clusters=10", "IICRegParameters.DecoderParams.num_subheads=3",
+                     "IICRegParameters.LossParams.paddings=[2,1,3]", "IICRegParameters.LossParams.patch_sizes=32"])
         rows = open(os.path.join(run_dir, "storage.csv")).read().splitlines()
         assert len(rows) == 3
         header = rows[0].split(",")
@@ -87,7 +81,7 @@ def test_main_entry_point_selects_the_benchmarked_arithmetic(monkeypatch, extra,
         return real(name, *a, **k)
     monkeypatch.setattr(ops, "call", spy)
     save = f"pytest_cli_prec_{expect}"
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    run_dir = th.run_dir(save)
     shutil.rmtree(run_dir, ignore_errors=True)
     try:
         argv = ["Trainer.name=udaiic", f"Trainer.save_dir={save}", "Trainer.device=cuda", "Trainer.max_epoch=2", "Trainer.num_batches=6",

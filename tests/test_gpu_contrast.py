@@ -2,34 +2,24 @@
 autograd of its closed form, determinism, refusals and the composed fallback, the NHWC average pool in every storage type, the
 projection head against float64 autograd, the epocher against the reference's own run (tests/golden/contrast.npz), a bf16 step and the
 CLI including fine-tuning from ``Pretrained=``."""
-import json
 import os
 import shutil
-import subprocess
-import sys
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
 import synth
+import trainer_harness as th
 from contrast_ref import closed_form, embeddings, golden_projector_state, golden_views, group_of
 from oracle import unet as OU
+from trainer_harness import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
 
 
-def _dump(tag, rows):
-    """With MISEG_ERROR_DUMP=<dir>, the achieved errors are written there as JSON (the numbers DESIGN.md section 14 quotes)."""
-    out = os.environ.get("MISEG_ERROR_DUMP")
-    if not out:
-        return
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, f"contrast_{tag}.json"), "w") as f:
-        json.dump(rows, f, indent=1)
+_dump = partial(th.error_dump, "contrast")          # the numbers DESIGN.md section 14 quotes
 
 
 def _rel(got, ref):
@@ -327,9 +317,7 @@ def _golden_run(g, dtype="float32"):
         crit.from_embeddings = inner
 
     def sampled(flat, name, param, tag):
-        o = opt.flat.offset_of(param)
-        got = flat[o:o + param.numel()].detach().cpu().numpy().reshape(-1).astype(np.float64)
-        return got[synth.sample_index(got.size, f"{tag}/{name}")]
+        return th.sampled(flat, opt.flat.offset_of(param), param.numel(), f"{tag}/{name}")
 
     now = model.state_dict()
     # plain data only: a model kept alive here would stay registered with the weight-pack cache for the rest of the session
@@ -438,13 +426,11 @@ def test_main_cli_pretrains_and_fine_tunes_from_pretrained():
     initialisation (which the pre-training never touched), one tiny epoch trains."""
     import yaml
     save = f"pytest_cli_contrast_{os.getpid()}"
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    run_dir = th.run_dir(save)
     ft = save + "_ft"
     try:
         shutil.rmtree(run_dir, ignore_errors=True)
-        res = subprocess.run([sys.executable, "semi_seg/main.py", "Trainer.name=contrast", "ContrastParameters.group_option=patient",
-                              f"Trainer.save_dir={save}", "Trainer.max_epoch=2"] + _TINY, cwd=PKG, capture_output=True, text=True, timeout=600)
-        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        th.run_main(["Trainer.name=contrast", "ContrastParameters.group_option=patient", f"Trainer.save_dir={save}", "Trainer.max_epoch=2"] + _TINY)
         files = set(os.listdir(run_dir))
         assert {"config.yaml", "last.pth", "storage.csv"} <= files and "best.pth" not in files, files
         cfg = yaml.safe_load(open(os.path.join(run_dir, "config.yaml")))
@@ -457,9 +443,9 @@ def test_main_cli_pretrains_and_fine_tunes_from_pretrained():
         assert sorted(ck["_projector"]) == ["_header.2.bias", "_header.2.weight", "_header.4.bias", "_header.4.weight"]
         assert ck["_buffers"]["_cur_epoch"] == 1
         assert len(ck["_optimizer"]["param_groups"][0]["params"]) == 5 * 6 + 4           # the encoder's and the projector's only
-        res = subprocess.run([sys.executable, "-c", _FINE_TUNE, "Trainer.name=partial", f"Pretrained={run_dir}", "Trainer.max_epoch=1"] + _TINY,
-                             cwd=PKG, capture_output=True, text=True, timeout=600, env={**os.environ, "CONTRAST_RUN": run_dir, "CONTRAST_FT": ft})
-        assert res.returncode == 0 and "fine-tuned from epoch 0 to 0" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
+        res = th.run_main(["Trainer.name=partial", f"Pretrained={run_dir}", "Trainer.max_epoch=1"] + _TINY, code=_FINE_TUNE,
+                          env={"CONTRAST_RUN": run_dir, "CONTRAST_FT": ft})
+        assert "fine-tuned from epoch 0 to 0" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
         ck2 = torch.load(os.path.join(run_dir + "_ft", "last.pth"), map_location="cpu", weights_only=False)
         assert ck2["_buffers"]["_cur_epoch"] == 0 and "_projector" not in ck2
     finally:

@@ -2,11 +2,9 @@
 max-pool kernels bit for bit against fp32 torch on the CPU computed from the stored inputs, their bias gradients against float64 sums,
 determinism and refusals, ``LocalProjectionHead`` against float64 autograd, the epocher against the reference's own run
 (tests/golden/contrast_decoder.npz), a bf16 run and the three-stage CLI chain."""
-import json
 import os
 import shutil
-import subprocess
-import sys
+from functools import partial
 
 import numpy as np
 import pytest
@@ -14,25 +12,17 @@ import torch
 import torch.nn.functional as F
 
 import synth
+import trainer_harness as th
 from contrast_decoder_ref import GROUPS, embed_rows, golden_projector_state, golden_views, group_of, pool_reference, same_bits
 from oracle import unet as OU
+from trainer_harness import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 SENTINEL = 3.0
 
 
-def _dump(tag, rows):
-    """With MISEG_ERROR_DUMP=<dir>, the achieved errors are written there as JSON (the numbers DESIGN.md section 15 quotes)."""
-    out = os.environ.get("MISEG_ERROR_DUMP")
-    if not out:
-        return
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, f"contrast_decoder_{tag}.json"), "w") as f:
-        json.dump(rows, f, indent=1)
+_dump = partial(th.error_dump, "contrast_decoder")          # the numbers DESIGN.md section 15 quotes
 
 
 def _rel(got, ref):
@@ -411,9 +401,7 @@ def _golden_run(g, dtype="float32"):
         crit.from_embeddings = inner
 
     def sampled(flat, name, param, tag):
-        o = opt.flat.offset_of(param)
-        got = flat[o:o + param.numel()].detach().cpu().numpy().reshape(-1).astype(np.float64)
-        return got[synth.sample_index(got.size, f"{tag}/{name}")]
+        return th.sampled(flat, opt.flat.offset_of(param), param.numel(), f"{tag}/{name}")
 
     now, now_projector = model.state_dict(), projector.state_dict()
     # plain data only: a model kept alive here would stay registered with the weight-pack cache for the rest of the session
@@ -532,17 +520,14 @@ def test_main_cli_runs_the_three_stages():
     blocks as it found them; run 3 starts at epoch 0 with run 2's ``Up_conv3`` weights."""
     import yaml
     save = f"pytest_cli_contrastdecoder_{os.getpid()}"
-    runs = os.path.join(PKG, "semi_seg", "runs")
-    r1, r2, r3 = (os.path.join(runs, f"{save}_{k}") for k in (1, 2, 3))
+    r1, r2, r3 = (th.run_dir(f"{save}_{k}") for k in (1, 2, 3))
     try:
         for d in (r1, r2, r3):
             shutil.rmtree(d, ignore_errors=True)
-        res = subprocess.run([sys.executable, "semi_seg/main.py", "Trainer.name=contrast", f"Trainer.save_dir={save}_1", "Trainer.max_epoch=1"] + _TINY,
-                             cwd=PKG, capture_output=True, text=True, timeout=600)
-        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
-        res = subprocess.run([sys.executable, "-c", _STAGE, "Trainer.name=contrastdecoder", f"Pretrained={r1}", f"Trainer.save_dir={save}_2",
-                              "Trainer.max_epoch=2"] + _TINY, cwd=PKG, capture_output=True, text=True, timeout=600, env={**os.environ, "STAGE_FROM": r1})
-        assert res.returncode == 0 and "stage done: epochs 0 to 1" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
+        th.run_main(["Trainer.name=contrast", f"Trainer.save_dir={save}_1", "Trainer.max_epoch=1"] + _TINY)
+        res = th.run_main(["Trainer.name=contrastdecoder", f"Pretrained={r1}", f"Trainer.save_dir={save}_2", "Trainer.max_epoch=2"] + _TINY,
+                          code=_STAGE, env={"STAGE_FROM": r1})
+        assert "stage done: epochs 0 to 1" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
         files = set(os.listdir(r2))
         assert {"config.yaml", "last.pth", "storage.csv"} <= files and "best.pth" not in files, files
         cfg = yaml.safe_load(open(os.path.join(r2, "config.yaml")))
@@ -563,9 +548,9 @@ def test_main_cli_runs_the_three_stages():
         assert frozen and all(torch.equal(m1[k], m2[k]) for k in frozen)
         assert all(torch.equal(m1[k], m2[k]) for k in m2 if k.startswith(UNTOUCHED))
         assert all(not torch.equal(m1[k], m2[k]) for k in trained)
-        res = subprocess.run([sys.executable, "-c", _STAGE, "Trainer.name=partial", f"Pretrained={r2}", f"Trainer.save_dir={save}_3", "Trainer.max_epoch=1"]
-                             + _TINY, cwd=PKG, capture_output=True, text=True, timeout=600, env={**os.environ, "STAGE_FROM": r2})
-        assert res.returncode == 0 and "stage done: epochs 0 to 0" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
+        res = th.run_main(["Trainer.name=partial", f"Pretrained={r2}", f"Trainer.save_dir={save}_3", "Trainer.max_epoch=1"] + _TINY,
+                          code=_STAGE, env={"STAGE_FROM": r2})
+        assert "stage done: epochs 0 to 0" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
         ck3 = torch.load(os.path.join(r3, "last.pth"), map_location="cpu", weights_only=False)
         assert ck3["_buffers"]["_cur_epoch"] == 0 and "_projector" not in ck3
     finally:

@@ -2,12 +2,10 @@
 float64 autograd (every class count, both powers, class weights, peaked logits, less than a wave, the grid-stride path, as the labeled
 part of a split batch, with a KL part), determinism, bad labels, refusals; the ``partial`` epocher against the reference's own run with
 the wheel's criterion (tests/golden/dice.npz), the step under the launch tape and the CLI."""
-import json
 import os
 import random
 import shutil
-import subprocess
-import sys
+from functools import partial
 
 import numpy as np
 import pytest
@@ -15,14 +13,11 @@ import torch
 
 import dice_ref
 import synth
-from oracle import unet as OU
+import trainer_harness as th
+from trainer_harness import DEV, FEATURES
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
-DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
-FEATURES = ["Conv5", "Up_conv3", "Up_conv2"]
 CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)
 # The project's bounds for a pixel loss (tests/test_gpu_entmin.py): the loss within 1e-5 relative, the gradient within 1e-5 of the
 # reference gradient's largest entry.  A torch fp32 evaluation of the same expression is within 6e-8 (loss) and 5e-7 (gradient) of
@@ -30,14 +25,7 @@ CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)
 LOSS_BOUND, GRAD_BOUND = 1e-5, 1e-5
 
 
-def _dump(tag, rows):
-    """With MISEG_ERROR_DUMP=<dir>, the achieved errors are written there as JSON (the numbers DESIGN.md section 25 quotes)."""
-    out = os.environ.get("MISEG_ERROR_DUMP")
-    if not out:
-        return
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, f"dice_{tag}.json"), "w") as f:
-        json.dump(rows, f, indent=1)
+_dump = partial(th.error_dump, "dice")          # the numbers DESIGN.md section 25 quotes
 
 
 def _nhwc(t):
@@ -273,55 +261,25 @@ def test_no_grad_is_forward_only_and_criteria_take_the_fused_path():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. the epocher
-def _unet(dtype, seed):
-    from contrastyou.arch import UNet
-    m = UNet(1, 4, compute_dtype=dtype)
-    m.load_state_dict(OU.init_state(1, 4, seed=seed))
-    return m.to(DEV)
-
-
 def _golden_run(g, monkeypatch):
     from deepclustering2.optim import Adam
-    from miseg_amd import unet_ops
     from semi_seg import epocher as E
     from semi_seg._utils import build_sup_criterion
-    cfg = {k[4:]: g[k].item() for k in g.files if k.startswith("cfg/")}
+    cfg = th.golden_cfg(g)
     H, LB, UB, NB = int(cfg["H"]), int(cfg["LB"]), int(cfg["UB"]), int(cfg["NB"])
-    model = _unet("float32", int(cfg["model_seed"]))
+    model = th.unet("float32", int(cfg["model_seed"]))
     opt = Adam(model.parameters(), lr=float(cfg["lr"]), weight_decay=float(cfg["wd"]))
     lab = [(T(synth.uniform(f"dice/lab{i}", (LB, 1, H, H))), T(synth.integers(f"dice/tgt{i}", (LB, 1, H, H), 4))) for i in range(NB)]
     unl = [T(synth.uniform(f"dice/unl{i}", (UB, 1, H, H))) for i in range(NB)]
-
-    def loader(imgs, tgts, B):
-        for img, tgt in zip(imgs, tgts):
-            yield [[[img, tgt], [img.clone(), tgt.clone()]], [f"patient{j:03d}_00_{j}" for j in range(B)], ["0"] * B,
-                   [f"patient{j:03d}_00" for j in range(B)]]
-
-    seeds = iter(int(s) for s in g["seeds"])
-    monkeypatch.setattr(E.random, "randint", lambda a, b: next(seeds))
-    grads, per_step = [], []
-    real_adam = unet_ops.adam_step
-
-    def adam_spy(param, grad, *a, **k):
-        if not grads:
-            grads.append(grad.detach().clone())
-        return real_adam(param, grad, *a, **k)
-
-    monkeypatch.setattr(unet_ops, "adam_step", adam_spy)
-    crit = build_sup_criterion({"SupCriterion": {"name": "dice"}}, 4)
-    ep = E.TrainEpocher(model, opt, loader([a for a, _ in lab], [b for _, b in lab], LB),
-                        loader(unl, [torch.zeros(UB, 1, H, H, dtype=torch.long)] * NB, UB), crit, 0.0, NB, 0, DEV,
-                        feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25])
-    ep._TAPE_DEFAULT = False
-    record = ep._record
-
-    def keep(host, *a):
-        per_step.append(dict(host))
-        record(host, *a)
-
-    ep._record = keep
-    res = ep.run()
-    monkeypatch.setattr(unet_ops, "adam_step", real_adam)
+    th.replay_seeds(monkeypatch, g["seeds"])
+    with th.adam_gradients(monkeypatch) as grads:
+        crit = build_sup_criterion({"SupCriterion": {"name": "dice"}}, 4)
+        ep = E.TrainEpocher(model, opt, th.reference_batches([a for a, _ in lab], [b for _, b in lab], LB),
+                            th.reference_batches(unl, [torch.zeros(UB, 1, H, H, dtype=torch.long)] * NB, UB), crit, 0.0, NB, 0, DEV,
+                            feature_position=FEATURES, feature_importance=th.IMPORTANCE)
+        ep._TAPE_DEFAULT = False
+        per_step = th.keep_records(ep)
+        res = ep.run()
     return res, grads[0].cpu(), per_step, opt
 
 
@@ -331,18 +289,9 @@ def test_partial_epocher_with_dice_matches_the_reference_run(golden, monkeypatch
     decoder tail after the last step."""
     g = golden("dice")
     res, grad, per_step, opt = _golden_run(g, monkeypatch)
-    names = [str(n) for n in g["param_names"]]
-    named = dict(zip(names, opt.flat.given))
+    named = dict(zip((str(n) for n in g["param_names"]), opt.flat.given))
     assert len(named) == len(opt.flat.given)
-    worst = {}
-    for n in names:
-        p = named[n]
-        o = opt.flat.offset_of(p)
-        got = grad[o:o + p.numel()].numpy().reshape(-1).astype(np.float64)
-        fp = synth.fp_unpack(g, f"grad_step1/{n}")
-        got = got[synth.sample_index(got.size, f"grad_step1/{n}")]
-        ref = fp["sample"].astype(np.float64)
-        worst[n] = float(np.linalg.norm(got - ref) / (np.linalg.norm(ref) + 1e-30))
+    worst = th.sampled_rel_l2(g, "grad_step1", grad, named, opt.flat.offset_of)
     tail = sorted(v for k, v in worst.items() if k.startswith(("Up_conv2", "DeConv")))
     print("dice golden gradients: logits layer", max(v for k, v in worst.items() if k.startswith("DeConv")), "tail", tail[0],
           tail[len(tail) // 2], tail[-1], "all", max(worst.values()))
@@ -356,14 +305,11 @@ def test_partial_epocher_with_dice_matches_the_reference_run(golden, monkeypatch
     print("dice golden steps:", per_step, list(g["sup_loss"]))
     np.testing.assert_allclose(per_step[0]["sup_loss"], g["sup_loss"][0], rtol=2e-5)
     np.testing.assert_allclose([s["sup_loss"] for s in per_step], g["sup_loss"], rtol=3e-3)
-    for n, q in named.items():
-        if not n.startswith(("Up_conv2", "DeConv_1x1")):
-            continue
-        fp = synth.fp_unpack(g, f"param_after/{n}")
-        got = q.detach().cpu().numpy().reshape(-1).astype(np.float64)[synth.sample_index(q.numel(), f"param_after/{n}")]
-        assert np.abs(got - fp["sample"]).max() <= 7.5e-3, (n, np.abs(got - fp["sample"]).max())
+    last = {n: q for n, q in named.items() if n.startswith(("Up_conv2", "DeConv_1x1"))}
+    for n, d in th.sampled_max_abs(g, "param_after", opt.flat.flat_param, last, opt.flat.offset_of).items():
+        assert d <= 7.5e-3, (n, d)
     keys = [str(k) for k in g["meter_keys"]]
-    got = {f"{k}/{kk}": float(vv) for k, v in res.items() for kk, vv in dict(v).items()}
+    got = th.meter_items(res)
     assert sorted(got) == sorted(keys), (sorted(got), sorted(keys))
     ref = dict(zip(keys, (float(v) for v in g["meter_values"])))
     np.testing.assert_allclose(got["sup_loss/mean"], ref["sup_loss/mean"], rtol=3e-3)
@@ -380,12 +326,12 @@ def test_without_the_section_the_first_step_is_the_softmax_kl_call(monkeypatch):
     from semi_seg.synthetic import SyntheticPairs
     crit = build_sup_criterion({}, 4)
     assert type(crit) is KL_div
-    model = _unet("float32", 41)
+    model = th.unet("float32", 41)
     opt = Adam(model.parameters(), lr=1e-3, weight_decay=1e-5)
     ep = E.TrainEpocher(model, opt, iter(SyntheticPairs(2, 64, 4, seed=0, device=DEV)), iter(SyntheticPairs(2, 64, 4, seed=1, device=DEV)),
-                        crit, 0.0, 1, 0, DEV, feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25])
+                        crit, 0.0, 1, 0, DEV, feature_position=FEATURES, feature_importance=th.IMPORTANCE)
     ep._TAPE_DEFAULT = False
-    seen, per_step = [], []
+    seen, per_step = [], th.keep_records(ep)
     real = E.supervised_loss
 
     def spy(criterion, logits, labels, *a, **k):
@@ -393,8 +339,6 @@ def test_without_the_section_the_first_step_is_the_softmax_kl_call(monkeypatch):
         return real(criterion, logits, labels, *a, **k)
 
     monkeypatch.setattr(E, "supervised_loss", spy)
-    record = ep._record
-    ep._record = lambda host, *a: (per_step.append(dict(host)), record(host, *a))
     random.seed(3)
     ep.run()
     assert len(seen) == 1 and seen[0][0] is crit and len(per_step) == 1
@@ -408,33 +352,14 @@ def build(name, dtype="float32", num_batches=7, **section):
     from semi_seg._utils import build_sup_criterion
     from semi_seg.epocher import TrainEpocher
     from semi_seg.synthetic import SyntheticPairs
-    model = _unet(dtype, 41)
+    model = th.unet(dtype, 41)
     opt = Adam(model.parameters(), lr=1e-3, weight_decay=1e-5)
     lab = SyntheticPairs(2, 64, 4, seed=0, device=DEV)
     unl = SyntheticPairs(2, 64, 4, seed=1, device=DEV)
     crit = build_sup_criterion({"SupCriterion": {"name": name, **section}}, 4)
     ep = TrainEpocher(model, opt, iter(lab), iter(unl), crit, 0.0, num_batches, 0, DEV, feature_position=FEATURES,
-                      feature_importance=[0.5, 0.25, 0.25])
+                      feature_importance=th.IMPORTANCE)
     return ep, model, opt
-
-
-def _run_steps(name, dtype, tape, steps=7, **section):
-    import bench
-    ep, model, opt = build(name, dtype, **section)
-    ep._TAPE_DEFAULT = False
-    drv = bench.StepDriver(ep)
-    if tape:
-        ep.enable_step_tape(warmup=2)
-    random.seed(11)
-    for _ in range(steps):
-        drv.step()
-    drv.close()
-    tp = ep._step_tape
-    info = None if tp is None else (tp.replays, tp.disabled, bool(tp.handle), tp.op_names())
-    st = {"param": opt.flat.flat_param.detach().clone(), "m": opt._m[0].detach().clone(), "v": opt._v[0].detach().clone(),
-          "meters": repr(dict(ep.meters.tracking_status()))}
-    ep.disable_step_tape()
-    return st, info
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
@@ -443,15 +368,12 @@ def test_tape_replay_equals_eager_steps(name, dtype):
     """2 eager + 1 recorded + 4 replayed iterations give the parameters, Adam's moments and the meters of 7 eager ones, bit for bit.
     The recorded iteration has no ATen launch (the tape would have been refused), one launch of the new entry point and no softmax-KL."""
     section = dict(kl_weight=0.7, dice_weight=1.3, pow=2) if name == "kldice" else {}
-    got, info = _run_steps(name, dtype, True, **section)
-    ref, _ = _run_steps(name, dtype, False, **section)
-    assert info is not None and info[1] is None, f"the tape was refused: {info[:3]}"
-    assert info[2] and info[0] == 4, f"expected 2 eager + 1 recorded + 4 replayed iterations: {info[:3]}"
-    names = info[3]
+    got, info = th.run_steps(lambda: build(name, dtype, **section), 7, True)
+    ref, _ = th.run_steps(lambda: build(name, dtype, **section), 7, False)
+    th.assert_replayed(info, 4)
+    names = info.op_names
     assert names.count("miseg_softmax_dice") == 1 and names.count("miseg_softmax_kl") == 0, names
-    for k in ("param", "m", "v"):
-        assert torch.equal(got[k], ref[k]), (k, float((got[k] - ref[k]).abs().max()))
-    assert got["meters"] == ref["meters"], (got["meters"], ref["meters"])
+    th.assert_same_state(got, ref, ("param", "m", "v", "meters"))
 
 
 def test_changed_dice_weight_rerecords_the_tape():
@@ -463,26 +385,18 @@ def test_changed_dice_weight_rerecords_the_tape():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. the CLI
-def _cli(save, extra, epochs):
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
-    shutil.rmtree(run_dir, ignore_errors=True)
-    res = subprocess.run(
-        [sys.executable, "semi_seg/main.py", f"Trainer.save_dir={save}", "Trainer.device=cuda", f"Trainer.max_epoch={epochs}",
-         "Trainer.num_batches=3", "Data.name=synthetic", "Data.size=64", "LabeledData.batch_size=2", "UnlabeledData.batch_size=2"] + extra,
-        cwd=PKG, capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
-    return run_dir
-
-
 @pytest.mark.parametrize("trainer,name,epochs,dtype", [("udaiic", "kldice", 2, "bfloat16"), ("meanteacher", "dice", 1, "float16")])
 def test_main_cli_runs_with_the_section(trainer, name, epochs, dtype):
     """``python semi_seg/main.py Trainer.name=<trainer> SupCriterion.name=<name>`` on synthetic data (bf16 storage, and fp16 with its
     loss scale): trains, validates with a finite loss, writes the section into config.yaml and the criterion's (small) subtree into
     the checkpoint."""
     save = f"pytest_cli_dice_{trainer}_{os.getpid()}"
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    run_dir = th.run_dir(save)
+    shutil.rmtree(run_dir, ignore_errors=True)
     try:
-        _cli(save, [f"Trainer.name={trainer}", f"SupCriterion.name={name}", "SupCriterion.pow=2", f"Arch.compute_dtype={dtype}"], epochs)
+        th.run_main([f"Trainer.save_dir={save}", "Trainer.device=cuda", f"Trainer.max_epoch={epochs}", "Trainer.num_batches=3",
+                     "Data.name=synthetic", "Data.size=64", "LabeledData.batch_size=2", "UnlabeledData.batch_size=2",
+                     f"Trainer.name={trainer}", f"SupCriterion.name={name}", "SupCriterion.pow=2", f"Arch.compute_dtype={dtype}"])
         files = set(os.listdir(run_dir))
         assert {"config.yaml", "last.pth", "storage.csv"} <= files, files
         import yaml

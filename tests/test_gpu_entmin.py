@@ -1,37 +1,22 @@
 """GPU: the `entmin` trainer (``Trainer.name=entmin``) -- the fused softmax-entropy kernel against float64
 autograd (plain and as a part of a split batch, every class count, peaked logits, the grid-stride path), determinism, refusals, the
 composed fallback, the epocher against the reference's own run (tests/golden/entmin.npz), the step under the launch tape and the CLI."""
-import json
 import os
-import random
 import shutil
-import subprocess
-import sys
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
 import synth
-from oracle import unet as OU
+import trainer_harness as th
+from trainer_harness import DEV, FEATURES
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
-DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
-FEATURES = ["Conv5", "Up_conv3", "Up_conv2"]
 CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)
-
-
-def _dump(tag, rows):
-    """With MISEG_ERROR_DUMP=<dir>, the achieved errors are written there as JSON (the numbers DESIGN.md section 13 quotes)."""
-    out = os.environ.get("MISEG_ERROR_DUMP")
-    if not out:
-        return
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, f"entmin_{tag}.json"), "w") as f:
-        json.dump(rows, f, indent=1)
+_dump = partial(th.error_dump, "entmin")          # the numbers DESIGN.md section 13 quotes
 
 
 def _logits(c, scale, shape=(3, 37, 53)):
@@ -215,54 +200,24 @@ def test_fused_path_returns_a_linear_loss_and_reports_entropy():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. the epocher
-def _unet(dtype, seed):
-    from contrastyou.arch import UNet
-    m = UNet(1, 4, compute_dtype=dtype)
-    m.load_state_dict(OU.init_state(1, 4, seed=seed))
-    return m.to(DEV)
-
-
 def _golden_run(g, monkeypatch):
     from deepclustering2.loss import KL_div
     from deepclustering2.optim import Adam
-    from miseg_amd import unet_ops
     from semi_seg import epocher as E
-    cfg = {k[4:]: g[k].item() for k in g.files if k.startswith("cfg/")}
+    cfg = th.golden_cfg(g)
     H, LB, UB, NB = int(cfg["H"]), int(cfg["LB"]), int(cfg["UB"]), int(cfg["NB"])
-    model = _unet("float32", int(cfg["model_seed"]))
+    model = th.unet("float32", int(cfg["model_seed"]))
     opt = Adam(model.parameters(), lr=float(cfg["lr"]), weight_decay=float(cfg["wd"]))
     lab = [(T(synth.uniform(f"entmin/lab{i}", (LB, 1, H, H))), T(synth.integers(f"entmin/tgt{i}", (LB, 1, H, H), 4))) for i in range(NB)]
     unl = [T(synth.uniform(f"entmin/unl{i}", (UB, 1, H, H))) for i in range(NB)]
-
-    def loader(imgs, tgts, B):
-        for img, tgt in zip(imgs, tgts):
-            yield [[[img, tgt], [img.clone(), tgt.clone()]], [f"patient{j:03d}_00_{j}" for j in range(B)], ["0"] * B,
-                   [f"patient{j:03d}_00" for j in range(B)]]
-
-    seeds = iter(int(s) for s in g["seeds"])
-    monkeypatch.setattr(E.random, "randint", lambda a, b: next(seeds))
-    grads, per_step = [], []
-    real_adam = unet_ops.adam_step
-
-    def adam_spy(param, grad, *a, **k):
-        if not grads:
-            grads.append(grad.detach().clone())
-        return real_adam(param, grad, *a, **k)
-
-    monkeypatch.setattr(unet_ops, "adam_step", adam_spy)
-    ep = E.EntropyMinEpocher(model, opt, loader([a for a, _ in lab], [b for _, b in lab], LB),
-                             loader(unl, [torch.zeros(UB, 1, H, H, dtype=torch.long)] * NB, UB), KL_div(verbose=False),
-                             float(cfg["weight"]), NB, 0, DEV, feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25])
-    ep._TAPE_DEFAULT = False
-    record = ep._record
-
-    def keep(host, *a):
-        per_step.append(dict(host))
-        record(host, *a)
-
-    ep._record = keep
-    res = ep.run()
-    monkeypatch.setattr(unet_ops, "adam_step", real_adam)
+    th.replay_seeds(monkeypatch, g["seeds"])
+    with th.adam_gradients(monkeypatch) as grads:
+        ep = E.EntropyMinEpocher(model, opt, th.reference_batches([a for a, _ in lab], [b for _, b in lab], LB),
+                                 th.reference_batches(unl, [torch.zeros(UB, 1, H, H, dtype=torch.long)] * NB, UB), KL_div(verbose=False),
+                                 float(cfg["weight"]), NB, 0, DEV, feature_position=FEATURES, feature_importance=th.IMPORTANCE)
+        ep._TAPE_DEFAULT = False
+        per_step = th.keep_records(ep)
+        res = ep.run()
     return res, grads[0].cpu(), per_step, opt
 
 
@@ -272,18 +227,9 @@ def test_epocher_matches_the_reference_run(golden, monkeypatch):
     the decoder tail after the last step."""
     g = golden("entmin")
     res, grad, per_step, opt = _golden_run(g, monkeypatch)
-    names = [str(n) for n in g["param_names"]]
-    named = dict(zip(names, opt.flat.given))
+    named = dict(zip((str(n) for n in g["param_names"]), opt.flat.given))
     assert len(named) == len(opt.flat.given)
-    worst = {}
-    for n in names:
-        p = named[n]
-        o = opt.flat.offset_of(p)
-        got = grad[o:o + p.numel()].numpy().reshape(-1).astype(np.float64)
-        fp = synth.fp_unpack(g, f"grad_step1/{n}")
-        got = got[synth.sample_index(got.size, f"grad_step1/{n}")]
-        ref = fp["sample"].astype(np.float64)
-        worst[n] = float(np.linalg.norm(got - ref) / (np.linalg.norm(ref) + 1e-30))
+    worst = th.sampled_rel_l2(g, "grad_step1", grad, named, opt.flat.offset_of)
     tail = sorted(v for k, v in worst.items() if k.startswith(("Up_conv2", "DeConv")))
     print("entmin golden gradients: logits layer", max(v for k, v in worst.items() if k.startswith("DeConv")), "tail", tail[0],
           tail[len(tail) // 2], tail[-1], "all", max(worst.values()))
@@ -303,14 +249,11 @@ def test_epocher_matches_the_reference_run(golden, monkeypatch):
     np.testing.assert_allclose([s["entropy"] for s in per_step], g["entropy"], rtol=3e-3)
     assert [s["reg_loss"] for s in per_step] == [s["entropy"] for s in per_step]
     # the decoder tail after 3 Adam steps: near-zero gradients' signs move a weight by up to 2 lr per step
-    for n, q in named.items():
-        if not n.startswith(("Up_conv2", "DeConv_1x1")):
-            continue
-        fp = synth.fp_unpack(g, f"param_after/{n}")
-        got = q.detach().cpu().numpy().reshape(-1).astype(np.float64)[synth.sample_index(q.numel(), f"param_after/{n}")]
-        assert np.abs(got - fp["sample"]).max() <= 7.5e-3, (n, np.abs(got - fp["sample"]).max())
+    last = {n: q for n, q in named.items() if n.startswith(("Up_conv2", "DeConv_1x1"))}
+    for n, d in th.sampled_max_abs(g, "param_after", opt.flat.flat_param, last, opt.flat.offset_of).items():
+        assert d <= 7.5e-3, (n, d)
     keys = [str(k) for k in g["meter_keys"]]
-    got = {f"{k}/{kk}": float(vv) for k, v in res.items() for kk, vv in dict(v).items()}
+    got = th.meter_items(res)
     assert sorted(got) == sorted(keys), (sorted(got), sorted(keys))
     ref = dict(zip(keys, (float(v) for v in g["meter_values"])))
     np.testing.assert_allclose(got["sup_loss/mean"], ref["sup_loss/mean"], rtol=3e-3)
@@ -324,32 +267,13 @@ def build(dtype="float32", num_batches=7, weight=1.0):
     from deepclustering2.optim import Adam
     from semi_seg.epocher import EntropyMinEpocher
     from semi_seg.synthetic import SyntheticPairs
-    model = _unet(dtype, 41)
+    model = th.unet(dtype, 41)
     opt = Adam(model.parameters(), lr=1e-3, weight_decay=1e-5)
     lab = SyntheticPairs(2, 64, 4, seed=0, device=DEV)
     unl = SyntheticPairs(2, 64, 4, seed=1, device=DEV)
     ep = EntropyMinEpocher(model, opt, iter(lab), iter(unl), KL_div(verbose=False), weight, num_batches, 0, DEV,
-                           feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25])
+                           feature_position=FEATURES, feature_importance=th.IMPORTANCE)
     return ep, model, opt
-
-
-def _run_steps(dtype, tape, steps=7, **kw):
-    import bench
-    ep, model, opt = build(dtype, **kw)
-    ep._TAPE_DEFAULT = False
-    drv = bench.StepDriver(ep)
-    if tape:
-        ep.enable_step_tape(warmup=2)
-    random.seed(11)
-    for _ in range(steps):
-        drv.step()
-    drv.close()
-    tp = ep._step_tape
-    info = None if tp is None else (tp.replays, tp.disabled, bool(tp.handle), tp.op_names())
-    st = {"param": opt.flat.flat_param.detach().clone(), "m": opt._m[0].detach().clone(), "v": opt._v[0].detach().clone(),
-          "meters": repr(dict(ep.meters.tracking_status()))}
-    ep.disable_step_tape()
-    return st, info
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
@@ -357,15 +281,12 @@ def test_entmin_tape_replay_equals_eager_steps(dtype):
     """2 eager + 1 recorded + 4 replayed iterations give the parameters, Adam's moments and the meters of 7 eager ones, bit for bit.
     The recorded iteration has no ATen launch (the tape would have been refused), one launch of the new entry point and no
     consistency kernel."""
-    got, info = _run_steps(dtype, True)
-    ref, _ = _run_steps(dtype, False)
-    assert info is not None and info[1] is None, f"the tape was refused: {info[:3]}"
-    assert info[2] and info[0] == 4, f"expected 2 eager + 1 recorded + 4 replayed iterations: {info[:3]}"
-    names = info[3]
+    got, info = th.run_steps(lambda: build(dtype), 7, True)
+    ref, _ = th.run_steps(lambda: build(dtype), 7, False)
+    th.assert_replayed(info, 4)
+    names = info.op_names
     assert names.count("miseg_softmax_entropy") == 1 and names.count("miseg_softmax_mse") == 0, names
-    for k in ("param", "m", "v"):
-        assert torch.equal(got[k], ref[k]), (k, float((got[k] - ref[k]).abs().max()))
-    assert got["meters"] == ref["meters"], (got["meters"], ref["meters"])
+    th.assert_same_state(got, ref, ("param", "m", "v", "meters"))
     assert "entropy" in got["meters"]
 
 
@@ -378,15 +299,8 @@ def test_changed_weight_rerecords_the_tape():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. the CLI
-def _cli(save, extra, epochs=2):
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
-    shutil.rmtree(run_dir, ignore_errors=True)
-    res = subprocess.run(
-        [sys.executable, "semi_seg/main.py", "Trainer.name=entmin", "EntropyMinParameters.weight=0.001", f"Trainer.save_dir={save}",
-         "Trainer.device=cuda", f"Trainer.max_epoch={epochs}", "Trainer.num_batches=3", "Data.size=64", "LabeledData.batch_size=2",
-         "UnlabeledData.batch_size=2"] + extra, cwd=PKG, capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
-    return run_dir
+_TINY = ["Trainer.device=cuda", "Trainer.max_epoch=2", "Trainer.num_batches=3", "Data.size=64", "LabeledData.batch_size=2",
+         "UnlabeledData.batch_size=2"]
 
 
 @pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
@@ -395,9 +309,10 @@ def test_main_cli_runs_entmin(golden, dtype):
     storage CSV with an entropy column; the checkpoint's key tree is the partial trainer's (tests/golden/trainer_io.npz) plus the
     entropy history (and, in fp16, the loss scaler); inference() runs on it in a fresh process."""
     save = f"pytest_cli_entmin_{dtype}_{os.getpid()}"
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    run_dir = th.run_dir(save)
+    shutil.rmtree(run_dir, ignore_errors=True)
     try:
-        _cli(save, [f"Arch.compute_dtype={dtype}"])
+        th.run_main(["Trainer.name=entmin", "EntropyMinParameters.weight=0.001", f"Trainer.save_dir={save}", f"Arch.compute_dtype={dtype}"] + _TINY)
         files = set(os.listdir(run_dir))
         assert {"config.yaml", "last.pth", "storage.csv"} <= files, files
         header = open(os.path.join(run_dir, "storage.csv")).read().splitlines()[0].split(",")
@@ -405,21 +320,15 @@ def test_main_cli_runs_entmin(golden, dtype):
         import yaml
         cfg = yaml.safe_load(open(os.path.join(run_dir, "config.yaml")))
         assert cfg["EntropyMinParameters"]["weight"] == 0.001
-        ck = torch.load(os.path.join(run_dir, "last.pth"), map_location="cpu", weights_only=False)
-        lines = synth.tree_lines(ck)
-        mine = sorted(l for l in lines if not l.startswith(("_storage/tra_entropy", "_optimizer/loss_scaler/")))
+        lines = th.checkpoint_tree(os.path.join(run_dir, "last.pth"))
+        mine = th.own_lines_removed(lines, ("_storage/tra_entropy", "_optimizer/loss_scaler/"))
         assert any(l.startswith("_storage/tra_entropy") for l in lines)
         assert any(l.startswith("_optimizer/loss_scaler/") for l in lines) == (dtype == "float16")
         ref = sorted(str(x) for x in golden("trainer_io")["partial/tree_last_pth"])
         assert mine == ref, (sorted(set(mine) - set(ref))[:12], sorted(set(ref) - set(mine))[:12])
-        code = ("import os, sys; from semi_seg.main import build_trainer; tr = build_trainer(sys.argv[1:]); "
-                "res, score = tr.inference(os.environ['ENTMIN_CKPT']); assert 0.0 <= score <= 1.0, score; print('inference', score)")
-        res = subprocess.run([sys.executable, "-c", code, "Trainer.name=entmin", f"Trainer.save_dir={save}_inf", "Trainer.device=cuda",
-                              "Trainer.max_epoch=2", "Trainer.num_batches=3", "Data.size=64", "LabeledData.batch_size=2",
-                              "UnlabeledData.batch_size=2", f"Arch.compute_dtype={dtype}"],
-                             cwd=PKG, capture_output=True, text=True, timeout=600,
-                             env={**os.environ, "ENTMIN_CKPT": os.path.join(run_dir, "last.pth")})
-        assert res.returncode == 0 and "inference" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
+        score = th.run_inference(["Trainer.name=entmin", f"Trainer.save_dir={save}_inf", f"Arch.compute_dtype={dtype}"] + _TINY,
+                                os.path.join(run_dir, "last.pth"))
+        assert 0.0 <= score <= 1.0, score
     finally:
         shutil.rmtree(run_dir, ignore_errors=True)
         shutil.rmtree(run_dir + "_inf", ignore_errors=True)

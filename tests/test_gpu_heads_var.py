@@ -4,8 +4,7 @@ T != 1, fp16 and bf16 storage, M > 64 in the global head, K = 64, the zero-norm 
 tests/heads_var_ref.py, (b) in properties that hold bit for bit, (c) in every refusal of the five entry points; and (d) the global
 IID-loss kernels (csrc/mi_global.hip) at K = 64 and N = 300.  The case tables, and why each shape is the smallest that reaches its
 branch, are in heads_var_ref.py; tests/test_cpu_heads_var.py checks the reference itself."""
-import json
-import os
+from functools import partial
 
 import numpy as np
 import pytest
@@ -13,21 +12,13 @@ import torch
 
 import heads_var_ref as V
 import synth
+import trainer_harness as th
 from oracle import iic as OI
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 T_ = torch.from_numpy
-
-
-def _dump(tag, rows):
-    """With MISEG_ERROR_DUMP=<dir>, the achieved errors are written there as JSON (the numbers DESIGN.md section 8, "Head variants against float64", quotes)."""
-    out = os.environ.get("MISEG_ERROR_DUMP")
-    if not out:
-        return
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, f"heads_var_{tag}.json"), "w") as f:
-        json.dump(rows, f, indent=1)
+_dump = partial(th.error_dump, "heads_var")          # the numbers DESIGN.md section 8, "Head variants against float64", quotes
 
 
 def _run(kind, case, feat, params, cot=None, src=None, flips="case", feat_grad=True, module=None):

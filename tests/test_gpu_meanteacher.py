@@ -13,22 +13,13 @@ import pytest
 import torch
 
 import synth
+import trainer_harness as th
 from oracle import unet as OU
+from trainer_harness import DEV, FEATURES, PKG, ROOT
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
-DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
-FEATURES = ["Conv5", "Up_conv3", "Up_conv2"]
 MT = dict(H=64, LB=2, UB=2, lr=1e-3, wd=1e-5, weight=10.0, alpha=0.999, ema_wd=1e-6)
-
-
-def _unet(dtype, seed):
-    from contrastyou.arch import UNet
-    m = UNet(1, 4, compute_dtype=dtype)
-    m.load_state_dict(OU.init_state(1, 4, seed=seed))
-    return m.to(DEV)
 
 
 def build(dtype="float32", num_batches=3, reg="mse"):
@@ -38,7 +29,7 @@ def build(dtype="float32", num_batches=3, reg="mse"):
     from deepclustering2.optim import Adam
     from semi_seg.epocher import MeanTeacherEpocher
     from semi_seg.synthetic import SyntheticPairs
-    model, teacher = _unet(dtype, 31), _unet(dtype, 32)
+    model, teacher = th.unet(dtype, 31), th.unet(dtype, 32)
     for p in teacher.parameters():
         p.detach_().requires_grad_(False)
     opt = Adam(model.parameters(), lr=MT["lr"], weight_decay=MT["wd"])
@@ -47,21 +38,13 @@ def build(dtype="float32", num_batches=3, reg="mse"):
     unl = SyntheticPairs(MT["UB"], MT["H"], 4, seed=1, device=DEV)
     crit = torch.nn.MSELoss() if reg == "mse" else KL_div(verbose=False)
     ep = MeanTeacherEpocher(model, teacher, opt, iter(lab), iter(unl), KL_div(verbose=False), crit, MT["weight"], num_batches, 0, DEV,
-                            feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25], ema_updater=upd)
+                            feature_position=FEATURES, feature_importance=th.IMPORTANCE, ema_updater=upd)
     return ep, model, teacher, opt, upd
 
 
-def _state(ep, model, teacher, opt, upd):
-    return {"student": opt.flat.flat_param.detach().clone(), "m": opt._m[0].detach().clone(), "v": opt._v[0].detach().clone(),
-            "teacher": upd._mirror.flat_param.detach().clone(),
-            "teacher_bn": [b.detach().clone() for b in teacher.buffers()]}
-
-
-def _assert_same(a, b):
-    for k in ("student", "m", "v", "teacher"):
-        assert torch.equal(a[k], b[k]), (k, float((a[k] - b[k]).abs().max()))
-    for x, y in zip(a["teacher_bn"], b["teacher_bn"]):
-        assert torch.equal(x, y)
+def _teacher_state(built):
+    ep, model, teacher, opt, upd = built
+    return {"teacher": upd._mirror.flat_param.detach().clone(), "teacher_bn": [b.detach().clone() for b in teacher.buffers()]}
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. the kernel
@@ -97,7 +80,7 @@ def test_ema_kernel_is_bit_equal_to_torch_eager_update():
 def test_ema_updater_call_matches_the_wheels_loop():
     """``ema_updater(teacher, student)`` on two networks: the wheel's per-tensor loop on copies, in torch on this device, bit-equal."""
     from deepclustering2.models import ema_updater
-    student, teacher = _unet("float32", 3), _unet("float32", 4)
+    student, teacher = th.unet("float32", 3), th.unet("float32", 4)
     ref = {k: v.clone() for k, v in teacher.state_dict().items()}
     upd = ema_updater(alpha=0.99, justify_alpha=True, weight_decay=1e-6)
     names = [n for n, _ in teacher.named_parameters()]
@@ -118,25 +101,8 @@ def test_ema_updater_call_matches_the_wheels_loop():
 
 # ---------------------------------------------------------------------------------------------------------------- 3. the tape
 def _run_steps(dtype, tape, steps=7):
-    import bench
-    from miseg_amd import ops
-    ops.set_mi_precision("fp32" if dtype == "float32" else "f16f8")
-    ep, model, teacher, opt, upd = build(dtype)
-    ep._TAPE_DEFAULT = False
-    drv = bench.StepDriver(ep)
-    if tape:
-        ep.enable_step_tape(warmup=2)
-    random.seed(11)
-    for _ in range(steps):
-        drv.step()
-    drv.close()
-    tp = ep._step_tape
-    info = None if tp is None else (tp.replays, tp.disabled, bool(tp.handle), tp.op_names())
-    st = _state(ep, model, teacher, opt, upd)
-    st["meters"] = repr(dict(ep.meters.tracking_status()))
-    ep.disable_step_tape()
-    ops.set_mi_precision("fp32")
-    return st, info
+    return th.run_steps(lambda: build(dtype), steps, tape, mi_precision="fp32" if dtype == "float32" else "f16f8",
+                        extra_state=_teacher_state)
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
@@ -146,13 +112,11 @@ def test_meanteacher_tape_replay_equals_eager_steps(dtype):
     EMA launch and packs the teacher's weights in the student's single pack launch."""
     got, info = _run_steps(dtype, True)
     ref, _ = _run_steps(dtype, False)
-    assert info is not None and info[1] is None, f"the tape was refused: {info[:3]}"
-    assert info[2] and info[0] == 4, f"expected 2 eager + 1 recorded + 4 replayed iterations: {info[:3]}"
-    names = info[3]
+    th.assert_replayed(info, 4)
+    names = info.op_names
     assert names.count("miseg_ema_update") == 1 and names.count("miseg_cat_flipped") == 1, names
     assert "miseg_pack_conv3x3_weights" not in names and names.count("miseg_pack_conv3x3_weights_multi") <= 1, names
-    _assert_same(got, ref)
-    assert got["meters"] == ref["meters"], (got["meters"], ref["meters"])
+    th.assert_same_state(got, ref, ("param", "m", "v", "teacher", "teacher_bn", "meters"))
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. resume
@@ -240,7 +204,7 @@ def test_training_forward_with_an_exhausted_accumulator_block(dtype):
     x = T(synth.uniform("mt/acc/x", (2, 1, 64, 64))).to(DEV)
     outs = []
     for exhausted in (False, True):
-        net = _unet(dtype, 41).train()
+        net = th.unet(dtype, 41).train()
         io = stepio.StepIO(DEV)
         io.upload(io.stage([], []))
         if exhausted:
@@ -278,7 +242,7 @@ def test_freeing_a_registered_network_rerecords_the_tape():
     from miseg_amd import unet_ops
     from miseg_amd.flat import FlatBuffers
     ep, model, teacher, opt, upd = build("float32")
-    other = _unet("float32", 51).train()
+    other = th.unet("float32", 51).train()
     fb = FlatBuffers(list(other.parameters()))
     fb.ensure()
     with torch.no_grad():
@@ -332,15 +296,12 @@ def test_main_cli_runs_meanteacher():
     """``python semi_seg/main.py Trainer.name=meanteacher``: one tiny synthetic epoch; the checkpoint holds the teacher and the
     updater."""
     save = f"pytest_cli_meanteacher_{os.getpid()}"
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    run_dir = th.run_dir(save)
     shutil.rmtree(run_dir, ignore_errors=True)
     try:
-        res = subprocess.run(
-            [sys.executable, "semi_seg/main.py", "Trainer.name=meanteacher", f"Trainer.save_dir={save}", "Trainer.device=cuda",
-             "Trainer.max_epoch=1", "Trainer.num_batches=5", "Data.size=64", "LabeledData.batch_size=2",
-             "UnlabeledData.batch_size=2", "Arch.compute_dtype=bfloat16"],
-            cwd=PKG, capture_output=True, text=True, timeout=600)
-        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        th.run_main(["Trainer.name=meanteacher", f"Trainer.save_dir={save}", "Trainer.device=cuda", "Trainer.max_epoch=1",
+                     "Trainer.num_batches=5", "Data.size=64", "LabeledData.batch_size=2", "UnlabeledData.batch_size=2",
+                     "Arch.compute_dtype=bfloat16"])
         sd = torch.load(os.path.join(run_dir, "last.pth"), map_location="cpu", weights_only=False)
         assert "_teacher_model" in sd and "_ema_updater" in sd and sd["_ema_updater"]["global_step"] == 5
         assert set(sd["_teacher_model"]) == set(sd["_model"])
@@ -355,11 +316,10 @@ def _golden_run(g, dtype, monkeypatch):
     from deepclustering2.loss import KL_div
     from deepclustering2.models import ema_updater
     from deepclustering2.optim import Adam
-    from miseg_amd import unet_ops
     from semi_seg import epocher as E
-    cfg = {k[4:]: g[k].item() for k in g.files if k.startswith("cfg/")}
+    cfg = th.golden_cfg(g)
     H, LB, NB = int(cfg["H"]), int(cfg["LB"]), int(cfg["NB"])
-    model, teacher = _unet(dtype, int(cfg["student_seed"])), _unet(dtype, int(cfg["teacher_seed"]))
+    model, teacher = th.unet(dtype, int(cfg["student_seed"])), th.unet(dtype, int(cfg["teacher_seed"]))
     for p in teacher.parameters():
         p.detach_().requires_grad_(False)
     opt = Adam(model.parameters(), lr=float(cfg["lr"]), weight_decay=float(cfg["wd"]))
@@ -367,43 +327,23 @@ def _golden_run(g, dtype, monkeypatch):
     batches = [(T(synth.uniform(f"mt/lab{i}", (LB, 1, H, H))), T(synth.integers(f"mt/tgt{i}", (LB, 1, H, H), 4))) for i in range(NB)]
 
     def loader():
-        for img, tgt in batches:
-            yield [[[img, tgt], [img.clone(), tgt.clone()]], [f"patient{j:03d}_00_{j}" for j in range(LB)], ["0"] * LB,
-                   [f"patient{j:03d}_00" for j in range(LB)]]
+        return th.reference_batches([a for a, _ in batches], [b for _, b in batches], LB)
 
-    seeds = iter(int(s) for s in g["seeds"])
-    monkeypatch.setattr(E.random, "randint", lambda a, b: next(seeds))
-    grads, teachers, per_step = [], [], []
-    real_adam, real_apply = unet_ops.adam_step, upd.apply
-
-    def adam_spy(param, grad, *a, **k):
-        if not grads:
-            grads.append(grad.detach().clone())
-        return real_adam(param, grad, *a, **k)
+    th.replay_seeds(monkeypatch, g["seeds"])
+    teachers, real_apply = [], upd.apply
 
     def apply_spy(*a, **k):
         real_apply(*a, **k)
         teachers.append(upd._mirror.flat_param.detach().clone())
 
-    monkeypatch.setattr(unet_ops, "adam_step", adam_spy)
     upd.apply = apply_spy
-    ep = E.MeanTeacherEpocher(model, teacher, opt, loader(), loader(), KL_div(verbose=False), torch.nn.MSELoss(), float(cfg["weight"]), NB,
-                              0, DEV, feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25], ema_updater=upd)
-    ep._TAPE_DEFAULT = False
-    record = ep._record
-
-    def keep(host, *a):
-        per_step.append(dict(host))
-        record(host, *a)
-
-    ep._record = keep
-    res = ep.run()
-    monkeypatch.setattr(unet_ops, "adam_step", real_adam)
+    with th.adam_gradients(monkeypatch) as grads:
+        ep = E.MeanTeacherEpocher(model, teacher, opt, loader(), loader(), KL_div(verbose=False), torch.nn.MSELoss(), float(cfg["weight"]),
+                                  NB, 0, DEV, feature_position=FEATURES, feature_importance=th.IMPORTANCE, ema_updater=upd)
+        ep._TAPE_DEFAULT = False
+        per_step = th.keep_records(ep)
+        res = ep.run()
     return res, grads[0].cpu(), teachers, per_step, opt, upd, teacher
-
-
-def _by_name(flat, fb, model):
-    return {n: flat[fb.offset_of(p):fb.offset_of(p) + p.numel()].view(p.shape).numpy() for n, p in model.named_parameters()}
 
 
 def test_epocher_matches_the_reference_run(golden, monkeypatch):
@@ -412,19 +352,10 @@ def test_epocher_matches_the_reference_run(golden, monkeypatch):
     its running statistics, the meter names (the reference's ``ds`` is ``sup_dice`` here, as in every epocher of semi_seg)."""
     g = golden("meanteacher")
     res, grad, teachers, per_step, opt, upd, teacher = _golden_run(g, "float32", monkeypatch)
-    model = opt.flat
-    names = [str(n) for n in g["param_names"]]
-    student_named = {n: p for n, p in zip([str(x) for x in g["param_names"]], opt.flat.given)}
-    assert len(student_named) == len(opt.flat.given)
+    named = dict(zip((str(n) for n in g["param_names"]), opt.flat.given))
+    assert len(named) == len(opt.flat.given)
     # 1. step-1 gradients
-    worst = {}
-    for n in names:
-        p = student_named[n]
-        o = model.offset_of(p)
-        got = grad[o:o + p.numel()].numpy().reshape(-1).astype(np.float64)
-        fp = synth.fp_unpack(g, f"grad_step1/{n}")
-        got = got[synth.sample_index(got.size, f"grad_step1/{n}")]
-        worst[n] = float(np.linalg.norm(got - fp["sample"]) / (np.linalg.norm(fp["sample"]) + 1e-30))
+    worst = th.sampled_rel_l2(g, "grad_step1", grad, named, opt.flat.offset_of)
     assert max(v for k, v in worst.items() if k.startswith("DeConv")) < 2e-5, worst
     tail = sorted(v for k, v in worst.items() if k.startswith(("Up_conv2", "DeConv")))
     assert tail[len(tail) // 2] < 5e-3 and tail[-1] < 1.5e-2, tail
@@ -438,26 +369,21 @@ def test_epocher_matches_the_reference_run(golden, monkeypatch):
     # 3. the teacher after the first (alpha 0: a copy of the student) and the last EMA: Adam's first steps move near-zero gradients' signs
     # by 2 lr, so the bound is in units of lr
     mirror = upd._mirror
+    for p in opt.flat.given:
+        assert mirror.offsets[[id(q) for q in opt.flat.params].index(id(p))] == opt.flat.offset_of(p)
     for i, flat in ((1, teachers[0]), (3, teachers[2])):
-        flat = flat.cpu()
-        for n, p in zip(names, opt.flat.given):
-            o = opt.flat.offset_of(p)
-            assert mirror.offsets[[id(q) for q in opt.flat.params].index(id(p))] == o
-            got = flat[o:o + p.numel()].numpy().reshape(-1).astype(np.float64)
-            fp = synth.fp_unpack(g, f"teacher{i}/{n}")
-            got = got[synth.sample_index(got.size, f"teacher{i}/{n}")]
-            assert np.abs(got - fp["sample"]).max() <= 2.5e-3 * i, (i, n, np.abs(got - fp["sample"]).max())
+        for n, d in th.sampled_max_abs(g, f"teacher{i}", flat, named, opt.flat.offset_of).items():
+            assert d <= 2.5e-3 * i, (i, n, d)
     errs = {}
     for n, b in teacher.named_buffers():
         if "running" in n:
-            fp = synth.fp_unpack(g, f"teacher3/{n}")
-            got = b.detach().cpu().numpy().reshape(-1).astype(np.float64)[synth.sample_index(b.numel(), f"teacher3/{n}")]
-            errs[n] = float(np.linalg.norm(got - fp["sample"]) / (np.linalg.norm(fp["sample"]) + 1e-30))
+            got, ref = th.sampled(b, 0, b.numel(), f"teacher3/{n}"), synth.fp_unpack(g, f"teacher3/{n}")["sample"]
+            errs[n] = float(np.linalg.norm(got - ref) / (np.linalg.norm(ref) + 1e-30))
     # measured: relative L2 1.5e-4 (Conv1) .. 1.4e-2 (Up5, behind the most ReLUs): the teacher's weights carry Adam's sign flips
     assert max(errs.values()) < 2e-2, errs
     # 4. meters
     ref_keys = [str(k).replace("ds/", "sup_dice/") for k in g["meter_keys"]]
-    got = {f"{k}/{kk}": float(vv) for k, v in res.items() for kk, vv in dict(v).items()}
+    got = th.meter_items(res)
     assert sorted(got) == sorted(ref_keys), (sorted(got), sorted(ref_keys))
     ref = dict(zip(ref_keys, (float(v) for v in g["meter_values"])))
     assert got["reg_weight/mean"] == ref["reg_weight/mean"] == 10.0

@@ -17,14 +17,12 @@ Found by this file: local_loss_finish_kernel added the (2 pad + 1)^2 per-displac
 terms of one sign) the whole-image loss of K = 60 / 58 was 2.5e-7 / 4.9e-7 off, outside 4 x the fp32 oracle's deviation + 1e-7; with the
 total kept in double it is 7.6e-9 / 4.9e-8.
 """
-import json
-import os
-
 import pytest
 import torch
 
 import mi_local_ref as M
 import synth
+import trainer_harness as th
 from test_gpu_mi import LOCAL_BWD_ATOL
 
 pytestmark = pytest.mark.gpu
@@ -52,12 +50,7 @@ def _record(name, quantity, err):
     written there as mi_local_variants.json: the figures of the docstring above."""
     row = _WORST.setdefault(name, {})
     row[quantity] = max(row.get(quantity, 0.0), float(err))
-    out = os.environ.get("MISEG_ERROR_DUMP")
-    if not out:
-        return
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, "mi_local_variants.json"), "w") as f:
-        json.dump(_WORST, f, indent=1, sort_keys=True)
+    th.error_dump("mi_local", "variants", _WORST, sort_keys=True)
 
 
 def _d(t):

@@ -13,7 +13,6 @@ One fault the suite cannot see, because it changes no bit: exchanging `rs` and `
 symmetrised joint Pw is (q + qt) / 2 at (i, j) and (qt + q) / 2 at (j, i) -- the same bits -- so the row sums and the column sums are
 added from the same numbers in the same order.
 """
-import json
 import os
 
 import pytest
@@ -21,6 +20,7 @@ import torch
 
 import mi_loss_ref as M
 import synth
+import trainer_harness as th
 from oracle import iic as OI
 
 pytestmark = pytest.mark.gpu
@@ -34,12 +34,8 @@ def _record(errors):
     mi_loss_errors.json: the figures of the docstring above."""
     for k, v in errors.items():
         _MAXIMA[k] = max(_MAXIMA.get(k, 0.0), float(v))
-    out = os.environ.get("MISEG_ERROR_DUMP")
-    if not out:
-        return
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, "mi_loss_errors.json"), "w") as f:
-        json.dump({k: {"kernel": v, "bound": M.bounds()[k]} for k, v in _MAXIMA.items()}, f, indent=1, sort_keys=True)
+    if os.environ.get("MISEG_ERROR_DUMP"):
+        th.error_dump("mi_loss", "errors", {k: {"kernel": v, "bound": M.bounds()[k]} for k, v in _MAXIMA.items()}, sort_keys=True)
 
 
 def _check(tag, errors):

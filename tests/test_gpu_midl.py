@@ -1,37 +1,23 @@
 """GPU: the `midl` trainer (``Trainer.name=midl``) -- the fused output local-MI kernels against float64 autograd,
 peaked predictions, fused against the generic composition, the epocher against the reference's own run (tests/golden/midl.npz), the
 step under the launch tape, the out-of-envelope fallback and the CLI."""
-import json
 import os
-import random
 import shutil
-import subprocess
-import sys
 import warnings
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
 import synth
-from oracle import iic as OI, unet as OU
+import trainer_harness as th
+from oracle import iic as OI
+from trainer_harness import DEV, FEATURES
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
-DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
-FEATURES = ["Conv5", "Up_conv3", "Up_conv2"]
-
-
-def _dump(tag, rows):
-    """With MISEG_ERROR_DUMP=<dir>, the achieved errors are written there as JSON (the numbers DESIGN.md section 12 quotes)."""
-    out = os.environ.get("MISEG_ERROR_DUMP")
-    if not out:
-        return
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, f"midl_{tag}.json"), "w") as f:
-        json.dump(rows, f, indent=1)
+_dump = partial(th.error_dump, "midl")          # the numbers DESIGN.md section 12 quotes
 
 
 def _flip64(x, masks):
@@ -176,57 +162,28 @@ def test_out_of_envelope_arguments_are_refused():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. the epocher
-def _unet(dtype, seed):
-    from contrastyou.arch import UNet
-    m = UNet(1, 4, compute_dtype=dtype)
-    m.load_state_dict(OU.init_state(1, 4, seed=seed))
-    return m.to(DEV)
-
-
 def _golden_run(g, geom, monkeypatch):
     from deepclustering2.loss import KL_div
     from deepclustering2.optim import Adam
-    from miseg_amd import ops, unet_ops
+    from miseg_amd import ops
     from semi_seg import epocher as E
-    cfg = {k[4:]: g[k].item() for k in g.files if k.startswith("cfg/")}
+    cfg = th.golden_cfg(g)
     H, LB, UB, NB = int(cfg["H"]), int(cfg["LB"]), int(cfg["UB"]), int(cfg["NB"])
     ops.set_mi_precision("fp32")
-    model = _unet("float32", int(cfg["model_seed"]))
+    model = th.unet("float32", int(cfg["model_seed"]))
     opt = Adam(model.parameters(), lr=float(cfg["lr"]), weight_decay=float(cfg["wd"]))
     lab = [(T(synth.uniform(f"midl/lab{i}", (LB, 1, H, H))), T(synth.integers(f"midl/tgt{i}", (LB, 1, H, H), 4))) for i in range(NB)]
     unl = [T(synth.uniform(f"midl/unl{i}", (UB, 1, H, H))) for i in range(NB)]
-
-    def loader(imgs, tgts, B):
-        for img, tgt in zip(imgs, tgts):
-            yield [[[img, tgt], [img.clone(), tgt.clone()]], [f"patient{j:03d}_00_{j}" for j in range(B)], ["0"] * B,
-                   [f"patient{j:03d}_00" for j in range(B)]]
-
-    seeds = iter(int(s) for s in g[f"{geom}/seeds"])
-    monkeypatch.setattr(E.random, "randint", lambda a, b: next(seeds))
-    grads, per_step = [], []
-    real_adam = unet_ops.adam_step
-
-    def adam_spy(param, grad, *a, **k):
-        if not grads:
-            grads.append(grad.detach().clone())
-        return real_adam(param, grad, *a, **k)
-
-    monkeypatch.setattr(unet_ops, "adam_step", adam_spy)
-    ep = E.MIDLTrainEpocher(model, opt, loader([a for a, _ in lab], [b for _, b in lab], LB),
-                            loader(unl, [torch.zeros(UB, 1, H, H, dtype=torch.long)] * NB, UB), KL_div(verbose=False),
-                            torch.nn.MSELoss(), NB, 0, DEV, feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25],
-                            cons_weight=float(cfg["cons_weight"]), iic_weight=float(cfg["iic_weight"]),
-                            padding=int(g[f"{geom}/cfg/padding"]), patch_size=int(g[f"{geom}/cfg/patch_size"]))
-    ep._TAPE_DEFAULT = False
-    record = ep._record
-
-    def keep(host, *a):
-        per_step.append(dict(host))
-        record(host, *a)
-
-    ep._record = keep
-    res = ep.run()
-    monkeypatch.setattr(unet_ops, "adam_step", real_adam)
+    th.replay_seeds(monkeypatch, g[f"{geom}/seeds"])
+    with th.adam_gradients(monkeypatch) as grads:
+        ep = E.MIDLTrainEpocher(model, opt, th.reference_batches([a for a, _ in lab], [b for _, b in lab], LB),
+                                th.reference_batches(unl, [torch.zeros(UB, 1, H, H, dtype=torch.long)] * NB, UB), KL_div(verbose=False),
+                                torch.nn.MSELoss(), NB, 0, DEV, feature_position=FEATURES, feature_importance=th.IMPORTANCE,
+                                cons_weight=float(cfg["cons_weight"]), iic_weight=float(cfg["iic_weight"]),
+                                padding=int(g[f"{geom}/cfg/padding"]), patch_size=int(g[f"{geom}/cfg/patch_size"]))
+        ep._TAPE_DEFAULT = False
+        per_step = th.keep_records(ep)
+        res = ep.run()
     return res, grads[0].cpu(), per_step, opt
 
 
@@ -237,18 +194,9 @@ def test_epocher_matches_the_reference_run(golden, monkeypatch, geom):
     test_gpu_step, per-step losses, the decoder tail after the last step, the meters."""
     g = golden("midl")
     res, grad, per_step, opt = _golden_run(g, geom, monkeypatch)
-    names = [str(n) for n in g["param_names"]]
-    named = dict(zip(names, opt.flat.given))
+    named = dict(zip((str(n) for n in g["param_names"]), opt.flat.given))
     assert len(named) == len(opt.flat.given)
-    worst = {}
-    for n in names:
-        p = named[n]
-        o = opt.flat.offset_of(p)
-        got = grad[o:o + p.numel()].numpy().reshape(-1).astype(np.float64)
-        fp = synth.fp_unpack(g, f"{geom}/grad_step1/{n}")
-        got = got[synth.sample_index(got.size, f"{geom}/grad_step1/{n}")]
-        ref = fp["sample"].astype(np.float64)
-        worst[n] = float(np.linalg.norm(got - ref) / (np.linalg.norm(ref) + 1e-30))
+    worst = th.sampled_rel_l2(g, f"{geom}/grad_step1", grad, named, opt.flat.offset_of)
     _dump(f"golden_grad_{geom}", worst)
     # the first-iteration bounds of test_gpu_step; measured on the logits layer: (a) 1.8e-5, (b) 6.1e-6.  (a)'s single 64 x 64 window
     # makes the MI gradient a small difference of entropies, computed in fp32 on both sides (DESIGN.md section 12)
@@ -267,14 +215,11 @@ def test_epocher_matches_the_reference_run(golden, monkeypatch, geom):
     np.testing.assert_allclose([s["uda"] for s in per_step], g[p + "uda"], rtol=2e-2)
     np.testing.assert_allclose([-s["mi"] for s in per_step], g[p + "mi_loss"], rtol=2e-2)
     # the decoder tail after 3 Adam steps: near-zero gradients' signs move a weight by up to 2 lr per step
-    for n, q in named.items():
-        if not n.startswith(("Up_conv2", "DeConv_1x1")):
-            continue
-        fp = synth.fp_unpack(g, f"{geom}/param_after/{n}")
-        got = q.detach().cpu().numpy().reshape(-1).astype(np.float64)[synth.sample_index(q.numel(), f"{geom}/param_after/{n}")]
-        assert np.abs(got - fp["sample"]).max() <= 7.5e-3, (n, np.abs(got - fp["sample"]).max())
+    last = {n: q for n, q in named.items() if n.startswith(("Up_conv2", "DeConv_1x1"))}
+    for n, d in th.sampled_max_abs(g, f"{geom}/param_after", opt.flat.flat_param, last, opt.flat.offset_of).items():
+        assert d <= 7.5e-3, (n, d)
     keys = [str(k) for k in g[p + "meter_keys"]]
-    got = {f"{k}/{kk}": float(vv) for k, v in res.items() for kk, vv in dict(v).items()}
+    got = th.meter_items(res)
     assert sorted(got) == sorted(keys), (sorted(got), sorted(keys))
     ref = dict(zip(keys, (float(v) for v in g[p + "meter_values"])))
     np.testing.assert_allclose(got["sup_loss/mean"], ref["sup_loss/mean"], rtol=3e-3)
@@ -289,36 +234,18 @@ def build(dtype="float32", num_batches=7, padding=1, patch_size=1024, iic_weight
     from deepclustering2.optim import Adam
     from semi_seg.epocher import MIDLTrainEpocher
     from semi_seg.synthetic import SyntheticPairs
-    model = _unet(dtype, 41)
+    model = th.unet(dtype, 41)
     opt = Adam(model.parameters(), lr=1e-3, weight_decay=1e-5)
     lab = SyntheticPairs(2, 64, 4, seed=0, device=DEV)
     unl = SyntheticPairs(2, 64, 4, seed=1, device=DEV)
     ep = MIDLTrainEpocher(model, opt, iter(lab), iter(unl), KL_div(verbose=False), torch.nn.MSELoss(), num_batches, 0, DEV,
-                          feature_position=FEATURES, feature_importance=[0.5, 0.25, 0.25], cons_weight=5.0, iic_weight=iic_weight,
+                          feature_position=FEATURES, feature_importance=th.IMPORTANCE, cons_weight=5.0, iic_weight=iic_weight,
                           padding=padding, patch_size=patch_size)
     return ep, model, opt
 
 
 def _run_steps(dtype, tape, steps=7, **kw):
-    import bench
-    from miseg_amd import ops
-    ops.set_mi_precision("fp32" if dtype == "float32" else "f16f8")
-    ep, model, opt = build(dtype, **kw)
-    ep._TAPE_DEFAULT = False
-    drv = bench.StepDriver(ep)
-    if tape:
-        ep.enable_step_tape(warmup=2)
-    random.seed(11)
-    for _ in range(steps):
-        drv.step()
-    drv.close()
-    tp = ep._step_tape
-    info = None if tp is None else (tp.replays, tp.disabled, bool(tp.handle), tp.op_names())
-    st = {"param": opt.flat.flat_param.detach().clone(), "m": opt._m[0].detach().clone(), "v": opt._v[0].detach().clone(),
-          "meters": repr(dict(ep.meters.tracking_status()))}
-    ep.disable_step_tape()
-    ops.set_mi_precision("fp32")
-    return st, info
+    return th.run_steps(lambda: build(dtype, **kw), steps, tape, mi_precision="fp32" if dtype == "float32" else "f16f8")
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
@@ -328,14 +255,11 @@ def test_midl_tape_replay_equals_eager_steps(dtype):
     adds into the consistency gradient (no assemble / add of its own)."""
     got, info = _run_steps(dtype, True)
     ref, _ = _run_steps(dtype, False)
-    assert info is not None and info[1] is None, f"the tape was refused: {info[:3]}"
-    assert info[2] and info[0] == 4, f"expected 2 eager + 1 recorded + 4 replayed iterations: {info[:3]}"
-    names = info[3]
+    th.assert_replayed(info, 4)
+    names = info.op_names
     assert names.count("miseg_iic_out_joint_fwd") == 1 and names.count("miseg_iic_out_bwd") == 1, names
     assert names.count("miseg_softmax_mse") == 1, names
-    for k in ("param", "m", "v"):
-        assert torch.equal(got[k], ref[k]), (k, float((got[k] - ref[k]).abs().max()))
-    assert got["meters"] == ref["meters"], (got["meters"], ref["meters"])
+    th.assert_same_state(got, ref, ("param", "m", "v", "meters"))
 
 
 def test_changed_mi_settings_rerecord_the_tape():
@@ -375,21 +299,14 @@ def test_taped_epocher_outside_the_envelope_stays_eager_with_a_warning():
     with warnings.catch_warnings(record=True) as caught:
         warnings.simplefilter("always")
         st, info = _run_steps("float32", True, steps=6, padding=5)
-    assert info is not None and info[1] is not None and not info[2] and info[0] == 0, info[:3]
+    assert info is not None and info.disabled is not None and not info.recorded and info.replays == 0, info[:3]
     assert any("launch tape not used" in str(w.message) for w in caught), [str(w.message) for w in caught]
     assert torch.isfinite(st["param"]).all()
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5. the CLI
-def _cli(save, extra, epochs=2):
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
-    shutil.rmtree(run_dir, ignore_errors=True)
-    res = subprocess.run(
-        [sys.executable, "semi_seg/main.py", "Trainer.name=midl", f"Trainer.save_dir={save}", "Trainer.device=cuda",
-         f"Trainer.max_epoch={epochs}", "Trainer.num_batches=3", "Data.size=64", "LabeledData.batch_size=2", "UnlabeledData.batch_size=2"]
-        + extra, cwd=PKG, capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
-    return run_dir
+_TINY = ["Trainer.device=cuda", "Trainer.max_epoch=2", "Trainer.num_batches=3", "Data.size=64", "LabeledData.batch_size=2",
+         "UnlabeledData.batch_size=2"]
 
 
 @pytest.mark.parametrize("dtype,extra", [("bfloat16", []), ("float16", []),
@@ -398,17 +315,18 @@ def test_main_cli_runs_midl(golden, dtype, extra):
     """``python semi_seg/main.py Trainer.name=midl``: two tiny epochs; config.yaml, last.pth and a storage CSV with uda and mi columns;
     the checkpoint's key tree is the uda trainer's (tests/golden/trainer_io.npz) plus the mi history; inference() runs on it."""
     save = f"pytest_cli_midl_{dtype}_{len(extra)}_{os.getpid()}"
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    run_dir = th.run_dir(save)
+    shutil.rmtree(run_dir, ignore_errors=True)
     try:
-        _cli(save, [f"Arch.compute_dtype={dtype}"] + extra)
+        th.run_main(["Trainer.name=midl", f"Trainer.save_dir={save}", f"Arch.compute_dtype={dtype}"] + _TINY + extra)
         files = set(os.listdir(run_dir))
         assert {"config.yaml", "last.pth", "storage.csv"} <= files, files
         header = open(os.path.join(run_dir, "storage.csv")).read().splitlines()[0].split(",")
         assert any(h.startswith("tra_uda") for h in header) and any(h.startswith("tra_mi") for h in header), header
-        ck = torch.load(os.path.join(run_dir, "last.pth"), map_location="cpu", weights_only=False)
         # the uda tree plus the mi history (and, in fp16 mode, the loss scaler every trainer's optimiser carries there)
-        mine = sorted(l for l in synth.tree_lines(ck) if not l.startswith(("_storage/tra_mi", "_optimizer/loss_scaler/")))
-        assert any(l.startswith("_storage/tra_mi") for l in synth.tree_lines(ck))
+        lines = th.checkpoint_tree(os.path.join(run_dir, "last.pth"))
+        mine = th.own_lines_removed(lines, ("_storage/tra_mi", "_optimizer/loss_scaler/"))
+        assert any(l.startswith("_storage/tra_mi") for l in lines)
         ref = sorted(str(x) for x in golden("trainer_io")["uda/tree_last_pth"])
         assert mine == ref, (sorted(set(mine) - set(ref))[:12], sorted(set(ref) - set(mine))[:12])
         if extra:
@@ -416,14 +334,9 @@ def test_main_cli_runs_midl(golden, dtype, extra):
             cfg = yaml.safe_load(open(os.path.join(run_dir, "config.yaml")))
             assert cfg["MIDLPaperParameters"]["padding"] == 3 and cfg["MIDLPaperParameters"]["patch_size"] == 32
         if dtype == "bfloat16" and not extra:
-            code = ("import os, sys; from semi_seg.main import build_trainer; tr = build_trainer(sys.argv[1:]); "
-                    "res, score = tr.inference(os.environ['MIDL_CKPT']); assert 0.0 <= score <= 1.0, score; print('inference', score)")
-            res = subprocess.run([sys.executable, "-c", code, "Trainer.name=midl", f"Trainer.save_dir={save}_inf", "Trainer.device=cuda",
-                                  "Trainer.max_epoch=2", "Trainer.num_batches=3", "Data.size=64", "LabeledData.batch_size=2",
-                                  "UnlabeledData.batch_size=2", f"Arch.compute_dtype={dtype}"],
-                                 cwd=PKG, capture_output=True, text=True, timeout=600,
-                                 env={**os.environ, "MIDL_CKPT": os.path.join(run_dir, "last.pth")})
-            assert res.returncode == 0 and "inference" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
+            score = th.run_inference(["Trainer.name=midl", f"Trainer.save_dir={save}_inf", f"Arch.compute_dtype={dtype}"] + _TINY,
+                                     os.path.join(run_dir, "last.pth"))
+            assert 0.0 <= score <= 1.0, score
     finally:
         shutil.rmtree(run_dir, ignore_errors=True)
         shutil.rmtree(run_dir + "_inf", ignore_errors=True)

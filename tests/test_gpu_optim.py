@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import optim_ref as R
+import trainer_harness as th
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
@@ -306,30 +307,15 @@ def _build(trainer, kind, dtype):
 
 
 def _run_steps(trainer, kind, dtype, tape, steps=8):
-    import bench
-    from miseg_amd import ops
-    ops.set_mi_precision("fp32" if dtype == "float32" else "f16f8")
-    try:
+    def build():
         random.seed(7)
-        ep, opt = _build(trainer, kind, dtype)
-        ep._TAPE_DEFAULT = False
-        drv = bench.StepDriver(ep)
-        if tape:
-            ep.enable_step_tape(warmup=2)
-        random.seed(11)
-        for _ in range(steps):
-            drv.step()
-        drv.close()
-        tp = ep._step_tape
-        info = None if tp is None else (tp.replays, tp.disabled, bool(tp.handle), tp.op_names())
-        state = {"p": opt.flat.flat_param.detach().clone(), "m": opt._m[0].detach().clone(), "v": opt._v[0].detach().clone()}
-        if kind != "RAdam":
-            state["vmax"] = opt._vmax[0].detach().clone()
-        out = state, repr(dict(ep.meters.tracking_status())), list(opt._steps), info
-        ep.disable_step_tape()
-        return out
-    finally:
-        ops.set_mi_precision("fp32")
+        return _build(trainer, kind, dtype)
+
+    def extra(built):
+        opt = built[1]
+        return {"steps": list(opt._steps), **({} if kind == "RAdam" else {"vmax": opt._vmax[0].detach().clone()})}
+
+    return th.run_steps(build, steps, tape, mi_precision="fp32" if dtype == "float32" else "f16f8", extra_state=extra)
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
@@ -339,15 +325,14 @@ def test_launch_tape_equals_eager_iterations_across_step_six(trainer, kind, dtyp
     """2 eager + 1 recorded + 5 replayed iterations against 8 eager ones, bit for bit: parameters, moments, running maximum, meters.
     The tape is recorded at step 3, where RAdam is not yet rectified, and replayed through steps 6-8, where it is: the step's scalars
     must come from the step block, not from the recorded call."""
-    got, meters_t, steps_t, info = _run_steps(trainer, kind, dtype, True)
-    ref, meters_e, steps_e, _ = _run_steps(trainer, kind, dtype, False)
-    assert info is not None and info[1] is None, f"the tape was refused: {info[:3]}"
-    assert info[2] and info[0] == 5, f"expected 2 eager + 1 recorded + 5 replayed iterations: {info[:3]}"
-    assert info[3].count("miseg_radam_step" if kind == "RAdam" else "miseg_adabound_step") == 1 and "miseg_adam_step_guarded" not in info[3]
-    assert steps_t == steps_e == [8]
-    for k in ref:
-        assert torch.equal(got[k], ref[k]), (k, float((got[k] - ref[k]).abs().max()))
-    assert float(ref["m"].abs().max()) > 0 and meters_t == meters_e, (meters_t, meters_e)
+    got, info = _run_steps(trainer, kind, dtype, True)
+    ref, _ = _run_steps(trainer, kind, dtype, False)
+    th.assert_replayed(info, 5)
+    names = info.op_names
+    assert names.count("miseg_radam_step" if kind == "RAdam" else "miseg_adabound_step") == 1 and "miseg_adam_step_guarded" not in names
+    assert got["steps"] == ref["steps"] == [8]
+    th.assert_same_state(got, ref, ("param", "m", "v", "meters") + (() if kind == "RAdam" else ("vmax",)))
+    assert float(ref["m"].abs().max()) > 0
 
 
 # ---------------------------------------------------------------------------------------------------- 6. Mean Teacher, 7. fp16 storage

@@ -3,7 +3,6 @@ vectors and against the PIL oracle -- bit-exact (u8 -> fp32 images, integer labe
 command on a dataset written in the reference's on-disk format."""
 import os
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -13,9 +12,9 @@ import torch
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-PKG = os.path.join(ROOT, "mi-based-regularized-semi-supervised-segmentation_amd")
 sys.path.insert(0, ROOT)
 
+import trainer_harness as th  # noqa: E402
 from oracle import augment as OA  # noqa: E402
 
 GOLD = np.load(os.path.join(HERE, "golden", "augment.npz"))
@@ -153,16 +152,13 @@ def test_main_cli_trains_on_acdc_format_dataset(tmp_path):
     """The reference's entry command on a dataset in the reference's on-disk format: 224^2 crops through udaiic."""
     root = _tree(tmp_path, train_patients=6, val_patients=2)
     save = "pytest_cli_acdc"
-    run_dir = os.path.join(PKG, "semi_seg", "runs", save)
+    run_dir = th.run_dir(save)
     shutil.rmtree(run_dir, ignore_errors=True)
     try:
-        res = subprocess.run(
-            [sys.executable, "semi_seg/main.py", "Trainer.name=udaiic", f"Trainer.save_dir={save}", "Trainer.device=cuda",
-             "Trainer.max_epoch=2", "Trainer.num_batches=3", "Data.name=acdc", f"Data.root={root}",
-             "Data.labeled_data_ratio=0.34", "Data.unlabeled_data_ratio=0.66", "LabeledData.batch_size=2",
-             "UnlabeledData.batch_size=3", "Arch.compute_dtype=bfloat16"],
-            cwd=PKG, capture_output=True, text=True, timeout=900)
-        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        res = th.run_main(["Trainer.name=udaiic", f"Trainer.save_dir={save}", "Trainer.device=cuda", "Trainer.max_epoch=2",
+                           "Trainer.num_batches=3", "Data.name=acdc", f"Data.root={root}", "Data.labeled_data_ratio=0.34",
+                           "Data.unlabeled_data_ratio=0.66", "LabeledData.batch_size=2", "UnlabeledData.batch_size=3",
+                           "Arch.compute_dtype=bfloat16"], timeout=900)
         assert "found" in res.stdout and "synthetic" not in res.stdout
         assert {"config.yaml", "last.pth"} <= set(os.listdir(run_dir))
     finally:

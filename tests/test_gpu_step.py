@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import synth
+import trainer_harness as th
 from oracle import heads as OH
 from oracle import unet as OU
 
@@ -170,16 +171,9 @@ def _first_iteration_gradients(mode, dtype, monkeypatch, wgrad_side=True, iic_si
     monkeypatch.setattr(unet_ops, "_WGRAD_SIDE", wgrad_side)
     monkeypatch.setenv("MISEG_IIC_STREAM", "1" if iic_side else "0")
     model, pw, lw, opt, lab, unl, kl = build(mode, dtype)
-    grabbed = []
-    real = unet_ops.adam_step
-
-    def spy(param, grad, *a, **k):
-        grabbed.append(grad.detach().clone())
-        return real(param, grad, *a, **k)
-
-    monkeypatch.setattr(unet_ops, "adam_step", spy)
-    random.seed(1234)
-    make_epocher(mode, model, pw, lw, opt, lab, unl, kl, [0.5, 0.25, 0.25], 1).run()
+    with th.adam_gradients(monkeypatch) as grabbed:
+        random.seed(1234)
+        make_epocher(mode, model, pw, lw, opt, lab, unl, kl, [0.5, 0.25, 0.25], 1).run()
     assert len(grabbed) == 1
     flat, fb = grabbed[0].cpu() / float(opt.grad_scale), opt.flat      # fp16 mode: the kernel divides the static loss scale out
     named = list(model.named_parameters()) + ([("proj/" + n, p) for n, p in pw.named_parameters()] if mode in ("udaiic", "iic") else [])
@@ -347,27 +341,14 @@ def test_deferred_readback_records_every_iteration_like_the_synchronous_one():
 
 def _tape_run(mode_dtype, mi_precision, tape: bool, steps: int = 7, trainer: str = "udaiic"):
     """`steps` iterations of the bench's step at a small shape; with the launch tape: 2 eager, 1 recorded, the rest replayed."""
-    import random
     import bench
-    from miseg_amd import ops
-    ops.set_mi_precision(mi_precision)
-    torch.manual_seed(0)
-    random.seed(7)
-    ep, opt = bench.build_step(torch.device("cuda"), 2, 2, 64, mode_dtype, 0)
-    ep._TAPE_DEFAULT = False
-    drv = bench.StepDriver(ep)
-    if tape:
-        ep.enable_step_tape(warmup=2)
-    random.seed(11)
-    for _ in range(steps):
-        drv.step()
-    drv.close()
-    tp = ep._step_tape
-    info = None if tp is None else (tp.replays, tp.disabled, tp.n_ops, bool(tp.handle))
-    out = opt.flat.flat_param.detach().clone(), opt._m[0].detach().clone(), dict(ep.meters.tracking_status()), opt._steps[0], info
-    ep.disable_step_tape()
-    ops.set_mi_precision("fp32")
-    return out
+
+    def build_step():
+        torch.manual_seed(0)
+        random.seed(7)
+        return bench.build_step(torch.device("cuda"), 2, 2, 64, mode_dtype, 0)
+
+    return th.run_steps(build_step, steps, tape, mi_precision=mi_precision, extra_state=lambda built: {"steps": built[1]._steps[0]})
 
 
 @pytest.mark.parametrize("dtype,mi", [("float32", "fp32"), ("bfloat16", "f16f8"), ("float16", "f16f8")])
@@ -376,14 +357,11 @@ def test_step_tape_replay_equals_eager_steps(dtype, mi):
     them again from one C call) must reproduce eager iterations bit for bit: same parameters, same Adam moments, same meters after a
     mix of eager warm-up, the recorded iteration and replays with fresh batches and fresh flip decisions -- and the shipped trainer
     must record clean (no ATen launch outside the library), i.e. the tape must really have been replayed."""
-    p_t, m_t, met_t, n_t, info = _tape_run(dtype, mi, True)
-    p_e, m_e, met_e, n_e, _ = _tape_run(dtype, mi, False)
-    assert info is not None and info[1] is None, f"the tape was refused: {info}"
-    assert info[3] and info[0] == 4, f"expected 2 eager + 1 recorded + 4 replayed iterations: {info}"
-    assert n_t == n_e == 7
-    assert torch.equal(p_e, p_t), float((p_e - p_t).abs().max())
-    assert torch.equal(m_e, m_t), float((m_e - m_t).abs().max())
-    assert repr(met_e) == repr(met_t), (met_e, met_t)     # repr: the unused lr meter is nan in both
+    got, info = _tape_run(dtype, mi, True)
+    ref, _ = _tape_run(dtype, mi, False)
+    th.assert_replayed(info, 4)
+    assert got["steps"] == ref["steps"] == 7
+    th.assert_same_state(got, ref, ("param", "m", "meters"))     # the meters' repr: the unused lr meter is nan in both
 
 
 def test_tape_guard_sees_the_backward_thread():
