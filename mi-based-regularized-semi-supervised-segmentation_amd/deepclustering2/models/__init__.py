@@ -66,10 +66,10 @@ class ema_updater:
 
     @torch.no_grad()
     def apply(self, ema_model: nn.Module, student_flat, coef: torch.Tensor, guard: Optional[torch.Tensor] = None) -> None:
-        from miseg_amd import unet_ops
+        from miseg_amd import packcache, unet_ops
         mirror = self.flats(ema_model, student_flat)
         unet_ops.ema_update(mirror.flat_param, student_flat.flat_param, coef, guard)
-        unet_ops.PACK_CACHE.invalidate()      # the teacher's masters changed: its packed operand copies are stale
+        packcache.PACK_CACHE.invalidate()      # the teacher's masters changed: its packed operand copies are stale
 
     @torch.no_grad()
     def __call__(self, ema_model: nn.Module, student_model: nn.Module):

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional
 import torch
 from torch import Tensor
 
-from . import unet_ops
+from . import packcache, unet_ops
 from ._cabi import call
 from ._rt import PinnedRing, _stream, fill_zero
 from .gradslot import adjacent_groups, grad_slot  # noqa: F401  (grad_slot: re-exported)
@@ -89,7 +89,7 @@ class FlatBuffers:
         self._offset_by_id = {id(p): o for p, o in zip(self.params, self.offsets)}
         OWNERS[id(self.given[0])] = self
         self.flat_param, self.flat_grad = flat_p, flat_g
-        unet_ops.PACK_CACHE.invalidate()
+        packcache.PACK_CACHE.invalidate()
 
     @staticmethod
     def _layout_order(params):
@@ -155,7 +155,7 @@ class MirrorBuffers:
     """One flat fp32 buffer for the parameters of a second network that follows ``like``'s layout exactly: same order, same
     offsets, same 16-byte padding (a Mean Teacher's teacher, whose parameters are an exponential moving average of the student's --
     the whole update is then ONE elementwise launch over the two buffers, ``unet_ops.ema_update``).  No gradient buffer: the
-    mirrored network is never trained.  Its conv weights are cached by ``unet_ops.PACK_CACHE`` like the optimiser's (``_miseg_mirror``),
+    mirrored network is never trained.  Its conv weights are cached by ``packcache.PACK_CACHE`` like the optimiser's (``_miseg_mirror``),
     so they are re-packed in the same single launch as the student's."""
 
     def __init__(self, params: List[torch.nn.Parameter], like: FlatBuffers):
@@ -191,7 +191,7 @@ class MirrorBuffers:
                 offsets.append(o)
         assert offsets == like.offsets
         self.params, self.offsets, self.flat_param = ordered, offsets, flat
-        unet_ops.PACK_CACHE.invalidate()
+        packcache.PACK_CACHE.invalidate()
 
     def ensure(self) -> None:
         if not self.valid():
@@ -367,7 +367,7 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
                     scale = -1.0                           # 1 / loss scale is hyper[4] of the step block
                 self._launch(gi, group, io.hyper(gi), scale, guard)
             self.last_guard = guard         # the flags that guarded the update (a Mean Teacher's EMA launch reads the same ones)
-            unet_ops.PACK_CACHE.invalidate()
+            packcache.PACK_CACHE.invalidate()
             return
         for gi, group in enumerate(self.param_groups):
             fb = self._flats[gi]
@@ -379,7 +379,7 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
                 guard = bad if guard is None else torch.cat([guard.reshape(-1), bad])
             self._launch(gi, group, self._hyper[gi], self.grad_scale, guard)
         self.last_guard = guard
-        unet_ops.PACK_CACHE.invalidate()   # the fp32 masters changed: packed operand copies are stale
+        packcache.PACK_CACHE.invalidate()   # the fp32 masters changed: packed operand copies are stale
 
     @torch.no_grad()
     def step(self, closure=None):

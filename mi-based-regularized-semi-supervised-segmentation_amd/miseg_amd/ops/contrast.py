@@ -11,7 +11,7 @@ from .. import _cabi
 from .._cabi import query
 from .._rt import _DT, _need_gpu, _ptr, _stream, _ws, as_nhwc, empty_nhwc
 from ..stepio import scalar_out
-from ..unet_ops import _pack
+from ..packcache import _pack
 from ._pkg import call
 
 _SUPCON_MAX_N, _SUPCON_MAX_D = 1024, 1024     # kSupMaxN / kSupMaxD of csrc/supcon.hip

@@ -29,7 +29,7 @@ import torch
 from torch import Tensor
 from torch.utils._python_dispatch import TorchDispatchMode
 
-from . import _cabi, stepio
+from . import _cabi, packcache, stepio
 from ._rt import _stream
 
 # ATen operators that launch nothing on the device: metadata, views, allocation.
@@ -149,12 +149,11 @@ class StepTape:
 
     # ------------------------------------------------------------------ per iteration
     def _key(self, io, li: Tensor, lt: Tensor, ui: Tensor, n_masks: int):
-        from . import unet_ops                      # upwards: unet_ops imports this module (keep)
         from .ops.mi import mi_precision_code       # upwards: ops is the top layer
         # the last four entries name persistent state the recorded pointers depend on -- the packed weights and their job table
         # (PACK_CACHE.generation) among them: a change releases the tape and re-records it
         return (tuple(li.shape), tuple(lt.shape), tuple(ui.shape), li.dtype, lt.dtype, ui.dtype, li.is_contiguous(), lt.is_contiguous(),
-                ui.is_contiguous(), n_masks, _stream(), mi_precision_code(), id(io), unet_ops.PACK_CACHE.generation,
+                ui.is_contiguous(), n_masks, _stream(), mi_precision_code(), id(io), packcache.PACK_CACHE.generation,
                 self.ep._model.training, self.ep._tape_signature(), id(getattr(self.ep, "_reducer", None)))
 
     _PERSISTENT = 4
@@ -183,11 +182,10 @@ class StepTape:
         """Before recording: collect unreachable objects (a network that is garbage already must not die while its weights sit in the
         recorded pack job table) and rebuild that table now, outside the recording.  True if the packed-weight generation moved."""
         import gc
-        from . import unet_ops                      # upwards, as in _key
-        before = unet_ops.PACK_CACHE.generation
+        before = packcache.PACK_CACHE.generation
         gc.collect()
-        unet_ops.PACK_CACHE.settle()
-        return unet_ops.PACK_CACHE.generation != before
+        packcache.PACK_CACHE.settle()
+        return packcache.PACK_CACHE.generation != before
 
     # ------------------------------------------------------------------ record
     def _record(self, io, li, lt, ui, flip_masks, key):

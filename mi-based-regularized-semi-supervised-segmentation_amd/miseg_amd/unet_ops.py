@@ -12,9 +12,6 @@ import os
 
 from typing import Optional, Tuple
 
-import struct
-import weakref
-
 import torch
 from torch import Tensor
 
@@ -22,16 +19,43 @@ from . import _cabi, stepio
 from ._cabi import call, query
 from ._rt import _DT, _GradJoin, _need_gpu, _ptr, _stream, _ws, as_nhwc, empty_nhwc, wait_stream
 from .gradslot import grad_slot
+from .packcache import _pack, _pack_now
 from .tape import keep
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
+
+# ---- switches (DESIGN.md, appendix "environment switches", and section 26 for the paths they select).  Module attributes, read when
+# a layer runs: tests patch them.  SYNC_COUNTERS.enabled (MISEG_BN_FINISH, below) and _rt._GradJoin.enabled are the other two.
+_WGRAD_SIDE = os.environ.get("MISEG_WGRAD_STREAM", "1") != "0"       # weight gradients on a side stream (_wgrad_fork); 0: the main stream
+_GRAPH_STREAMS = os.environ.get("MISEG_GRAPH_STREAMS", "1") == "1"   # fork side streams inside a captured step too (side_streams_allowed)
+_STEM_KERNELS = os.environ.get("MISEG_STEM_KERNELS", "1") != "0"     # the stem through its own kernels (_forward_plan); 0: the MFMA path
+_STEM_DGRAD = os.environ.get("MISEG_STEM_DGRAD", "1") != "0"         # the image gradient through miseg_conv3x3_stem_dgrad; 0: the generic path
+_BN_ACC = os.environ.get("MISEG_BN_ACC", "1") != "0"                 # forward statistics as fixed-point accumulators; 0: partial rows + finalize
+_BN_ACC_BWD = os.environ.get("MISEG_BN_ACC_BWD", "0") == "1"         # the same for the backward's sums (measured slower: OFF)
+_FUSE_UPS_DGRAD = True   # False: conv3x3 dgrad + miseg_sumpool2x2 as two launches
+_DUAL_DGRAD = True       # concat layers: one data-gradient launch with two destinations (False: one launch per source)
+_FUSE_BN_BWD = os.environ.get("MISEG_BN_FUSE", "0") == "1"           # BatchNorm backward folded into the convolutions (_backward_fused; measured slower: OFF)
+# The statistics pass ALONE in the producing data-gradient kernel's epilogue (no loader transform): MISEG_BN_RED=1 (round-4 experiment)
+_RED_ONLY = os.environ.get("MISEG_BN_RED", "0") == "1" and not _FUSE_BN_BWD
+_STEM_MAX_W = 1022                  # the stem kernels keep whole image rows (+ halo) in 4 x 256 registers
+
+
+def side_streams_allowed() -> bool:
+    """May this code fork a side stream now?  Under hipGraph capture the fork/join (wait_stream both ways) is captured as graph
+    dependencies; ``MISEG_GRAPH_STREAMS=0`` keeps a captured step on one stream."""
+    return _GRAPH_STREAMS or not torch.cuda.is_current_stream_capturing()
+
+
+def _epilogue_sums_allowed() -> bool:
+    """May a data-gradient epilogue take the source layer's BatchNorm-backward sums?  With the folded backward (which includes the
+    statistics pass in the producing data-gradient kernel's epilogue) or with that pass alone (``_RED_ONLY``)."""
+    return _FUSE_BN_BWD or _RED_ONLY
+
 
 # ---- weight gradients off the critical path
 # In the U-Net backward only BN-backward -> dgrad feeds the next layer; a layer's wgrad (+ its split reduction) has no consumer
 # before the optimiser.  It is launched on a side stream so the dgrad chain does not queue behind it and the two fill each
 # other's tails.  Joined before anything reads the flat gradient buffer (FlatBuffers.collect, GradReducer._launch).
-_WGRAD_SIDE = os.environ.get("MISEG_WGRAD_STREAM", "1") != "0"
-_GRAPH_STREAMS = os.environ.get("MISEG_GRAPH_STREAMS", "1") == "1"   # fork side streams inside a captured step too
 _wgrad_streams: dict = {}
 _wgrad_dirty: set = set()
 
@@ -52,30 +76,6 @@ def join_wgrad_streams() -> None:
         if cur != _wgrad_streams[dev]:
             wait_stream(cur, _wgrad_streams[dev])
             _wgrad_dirty.discard(dev)
-
-
-_FUSE_UPS_DGRAD = True   # False: conv3x3 dgrad + miseg_sumpool2x2 as two launches
-_DUAL_DGRAD = True       # concat layers: one data-gradient launch with two destinations (False: one launch per source)
-# BatchNorm backward folded into the convolutions around it (layers without the fused pool): the statistics pass leaves six
-# coefficients per channel, the data- and weight-gradient kernels form graw in their loaders (no bn_bwd_apply pass, no graw tensor),
-# and a data-gradient launch whose output is the activation gradient of ANOTHER such layer takes that layer's statistics pass in its
-# epilogue (no bn_relu_bwd_reduce pass there).  OFF by default (MISEG_BN_FUSE=1 turns it on): measured slower, DESIGN.md section 9.
-_FUSE_BN_BWD = os.environ.get("MISEG_BN_FUSE", "0") == "1"
-_FUSE_BN_RED = True      # ... including the statistics pass in the producing data-gradient kernel's epilogue
-# The statistics pass ALONE in the producing data-gradient kernel's epilogue (no loader transform): MISEG_BN_RED=1 (round-4 experiment)
-_RED_ONLY = os.environ.get("MISEG_BN_RED", "0") == "1" and not _FUSE_BN_BWD
-# 1 (default): the forward statistics leave the convolution as fixed-point atomic adds and the apply kernel finishes them itself
-# (miseg_conv3x3_fwd_acc / miseg_bn_relu_fwd_acc): 22 launches fewer per step.  0: one partial row per block + miseg_bn_finalize.
-# The stem (one image channel) through its own pixel-per-thread kernels reading the fp32 image, instead of the streaming MFMA convolution
-# and the tiled weight gradient on a padded channel vector: the kernels themselves are on a par (50 vs 50 us forward, 52 + 7 vs 59 + 10 us
-# weight gradient -- the step's last kernel), the padded operand's 15 us launch becomes 4: -0.02 ms per step.  0: the MFMA path.
-_STEM_KERNELS = os.environ.get("MISEG_STEM_KERNELS", "1") != "0"
-_STEM_MAX_W = 1022                  # the stem kernels keep whole image rows (+ halo) in 4 x 256 registers
-_BN_ACC = os.environ.get("MISEG_BN_ACC", "1") != "0"
-# The same for the backward's sums (two fixed-point tiers, miseg_bn_relu_bwd_dual_acc).  Built and measured, OFF: the reduce kernel's
-# blocks all finish together, so their atomics arrive as one burst on a few lines (+8 us per launch) and the apply prologue costs 5 us
-# -- more than the finalize launch they replace (6 us + a launch boundary).  DESIGN.md section 10.
-_BN_ACC_BWD = os.environ.get("MISEG_BN_ACC_BWD", "0") == "1"
 
 
 class _BnRec:
@@ -162,56 +162,47 @@ def vec_of(dtype) -> int:
 
 # ---- gradients with respect to the input image, and forward passes that leave the running statistics alone (virtual adversarial
 # training; saliency maps and adversarial evaluation need the first too)
-# The stem's data gradient through its own pixel-per-thread kernel (miseg_conv3x3_stem_dgrad); 0: the generic path (the streaming /
-# tiled convolution over a dgrad-packed weight whose input channels are padded to one vector; channel 0 of its output).
-_STEM_DGRAD = os.environ.get("MISEG_STEM_DGRAD", "1") != "0"
+# _STEM_DGRAD: the stem's data gradient through its own pixel-per-thread kernel (miseg_conv3x3_stem_dgrad); 0: the generic path (the
+# streaming / tiled convolution over a dgrad-packed weight whose input channels are padded to one vector; channel 0 of its output).
 _bn_untracked = False
 _data_grad_only = False
 _bn_float_stats = False
 
 
 @contextlib.contextmanager
+def _mode(flag: str):
+    """Set the module-level mode ``flag`` for the duration of a ``with`` block."""
+    prev, globals()[flag] = globals()[flag], True
+    try:
+        yield
+    finally:
+        globals()[flag] = prev
+
+
 def bn_untracked():
     """Training-mode forwards inside this block normalise with the batch statistics and leave ``running_mean``, ``running_var`` and
     ``num_batches_tracked`` untouched (``track_running_stats`` switched off, as the wheel's ``_disable_tracking_bn_stats`` does): the
     BatchNorm kernels get null pointers for the three, which every forward variant -- accumulator, counter, finalize, stem -- takes as
     "do not track".  Outputs and ``saved`` coefficients are those of a tracked pass.  Evaluation-mode forwards are not affected."""
-    global _bn_untracked
-    prev, _bn_untracked = _bn_untracked, True
-    try:
-        yield
-    finally:
-        _bn_untracked = prev
+    return _mode("_bn_untracked")
 
 
-@contextlib.contextmanager
 def bn_float_statistics():
     """Training-mode forwards inside this block take their batch statistics from the float partial sums (one row per convolution
     block + ``miseg_bn_finalize``, or the last-block counter form), not from the fixed-point accumulators: the path ``MISEG_BN_ACC=0``
     selects, for these forwards only.  For computations that DIFFERENCE two forward passes of nearly the same input (VAT's direction at
     a small ``xi``): with the accumulators the direction after one iteration at ``xi = 0.1`` was measured 1.6e-3 from the float64
     reference, with the float sums 1.3e-4, where a float32 evaluation on the CPU lands at 9e-5."""
-    global _bn_float_stats
-    prev, _bn_float_stats = _bn_float_stats, True
-    try:
-        yield
-    finally:
-        _bn_float_stats = prev
+    return _mode("_bn_float_stats")
 
 
-@contextlib.contextmanager
 def data_grad_only():
     """Forwards inside this block build a graph whose backward DELIVERS data gradients only: no weight-gradient launch of the 3x3
     convolutions, no flat-gradient slot claimed or written, ``param.grad`` untouched, no weight-gradient side stream.  Two sums are
     still formed and dropped, into scratch: gamma's and beta's (the BatchNorm data gradient needs them anyway) and the 1x1 head's
     weight and bias sums, which its one backward kernel forms in the pass that writes the data gradient (68 multiply-adds per pixel).  The flag is read when the
     forward runs and travels in the node, so the backward may run after the block has been left (VAT's direction pass)."""
-    global _data_grad_only
-    prev, _data_grad_only = _data_grad_only, True
-    try:
-        yield
-    finally:
-        _data_grad_only = prev
+    return _mode("_data_grad_only")
 
 
 class _StemSink:
@@ -282,133 +273,44 @@ def _stem_operand(image: Tensor, dtype) -> Tensor:
     return out
 
 
-def _pack_now(weight: Tensor, dtype, kind: int, ci_begin: int, ci_count: int, packed: Optional[Tensor] = None, cin: Optional[int] = None) -> Tensor:
-    cout, cin_w = weight.shape[0], weight.shape[1]
-    kind &= 0xff
-    if cin is not None and cin != cin_w:      # forward layout of a weight with fewer input channels than the (padded) activation
-        assert kind == 0 and cin > cin_w, (kind, cin, cin_w)
-        kind, ci_count = cin_w << 8, cin
-    else:
-        cin = cin_w
-    if packed is None:
-        packed = torch.empty((ci_count if kind & 0xff else cout) * (cout if kind & 0xff else cin) * 9, dtype=dtype, device=weight.device)
-    call("miseg_pack_conv3x3_weights", _stream(), _DT[dtype], _ptr(weight), cout, cin, kind, ci_begin, ci_count, _ptr(packed))
-    return packed
+# ---- the forward plan: which statistics path a layer takes, decided before anything is launched or allocated
+_EVAL, _COUNTER, _ACC, _ROWS = "eval", "counter", "acc", "rows"
 
 
-_NO_PACK_CACHE = False
-
-
-class _PackCache:
-    """Operand-layout copies of the conv weights, refreshed once per optimiser step in ONE launch.
-
-    The U-Net asks for ~47 packed weight tensors per step (forward layout + one dgrad layout per concat source); they
-    only change when the optimiser (or anything else that bumps ``epoch`` / the tensor version) rewrites the masters.
-    The first request after such a change re-packs every registered weight with ``miseg_pack_conv3x3_weights_multi``;
-    the rest of the step are dictionary hits.  Only parameters that live in a flat buffer are cached (their storage is
-    stable: the optimiser's, or a Mean Teacher's mirror of it, ``flat.MirrorBuffers``); anything else is packed on the spot.
-
-    ``generation`` names the set of packed tensors and the device job table: a launch tape records both addresses, so the
-    generation moves whenever either changes -- a new entry, a registered weight that died (its weak reference's callback, so
-    that the very next step sees it, before anything is replayed), and every rebuild of the job table."""
-
-    def __init__(self):
-        self.epoch = 0            # bumped by FusedAdam.step / FlatBuffers.build / load_state_dict
-        self.entries = {}         # key -> entry list, see get()
-        self.packed_epoch = -1
-        self.jobs_dev = {}        # dtype -> (device job table, njobs, total_blocks, keys)
-        self.dirty = True
-        self.generation = 0       # bumped whenever the set of packed tensors (hence the addresses a launch tape recorded) changes
-
-    def invalidate(self) -> None:
-        self.epoch += 1
-
-    def _died(self, _ref) -> None:
-        self.dirty = True
-        self.generation += 1
-
-    def get(self, weight: Tensor, dtype, kind: int, cb: int, cs: int, cin: Optional[int] = None) -> Tensor:
-        """``cin`` (forward layout only): input channels of the PACKED tensor when the weight has fewer (the stem); the kind word then
-        carries the weight's own count in its high bits (miseg_pack_conv3x3_weights)."""
-        if (getattr(weight, "_miseg_grad_slot", None) is None and not getattr(weight, "_miseg_mirror", False)) or not weight.is_cuda \
-                or _NO_PACK_CACHE:
-            return _pack_now(weight, dtype, kind, cb, cs, cin=cin)
-        key = (weight.data_ptr(), tuple(weight.shape), dtype, kind, cb, cs)
-        ent = self.entries.get(key)
-        if ent is None or ent[0]() is not weight:
-            # entry: [weakref(weight), dtype, kind, cb, cs, packed, version packed at, epoch packed at]
-            ent = self.entries[key] = [weakref.ref(weight, self._died), dtype, kind, cb, cs, _pack_now(weight, dtype, kind, cb, cs, cin=cin),
-                                       weight._version, self.epoch]
-            self.dirty = True
-            self.generation += 1
-            return ent[5]
-        if self.packed_epoch != self.epoch:
-            self._repack_all()
-        if ent[6] != weight._version or ent[7] != self.epoch:   # edited in place since / registered after the batch
-            _pack_now(weight, dtype, kind, cb, cs, ent[5], cin=cin)
-            ent[6], ent[7] = weight._version, self.epoch
-        return ent[5]
-
-    def settle(self) -> None:
-        """Drop the entries of weights that died and rebuild the job table if that (or a new entry) left it stale; no packing."""
-        if self.dirty or any(ent[0]() is None for ent in self.entries.values()):
-            self.packed_epoch = -1            # the next request packs everything (one launch, from the new table)
-            self._repack_all(launch=False)
-
-    def _repack_all(self, launch: bool = True) -> None:
-        dead = [k for k, ent in self.entries.items() if ent[0]() is None]   # parameters that no longer exist
-        for k in dead:
-            del self.entries[k]
-        if (dead or self.dirty) and torch.cuda.is_current_stream_capturing():
-            # the job table would need a host->device copy, which a capturing stream does not allow: pack one by one
-            for ent in self.entries.values():
-                w = ent[0]()
-                _pack_now(w, ent[1], ent[2] & 0xff, ent[3], ent[4], ent[5], cin=(ent[4] if ent[2] >> 8 else None))
-                ent[6], ent[7] = w._version, self.epoch
-            self.packed_epoch = self.epoch
-            return
-        if dead or self.dirty:
-            self.jobs_dev = {}            # frees the old table: a tape that recorded its address must re-record (generation below)
-            by_dtype = {}
-            for ent in self.entries.values():
-                by_dtype.setdefault(ent[1], []).append(ent)
-            for dtype, ents in by_dtype.items():
-                blob, first = bytearray(), 0
-                for ent in ents:
-                    w, packed = ent[0](), ent[5]
-                    cin_packed = ent[4] if ent[2] >> 8 else w.shape[1]      # stem: packed with more input channels than the weight has
-                    blob += struct.pack("<QQiiiiii", w.data_ptr(), packed.data_ptr(), w.shape[0], cin_packed, ent[2], ent[3], ent[4], first)
-                    first += (packed.numel() + 255) // 256
-                table = torch.frombuffer(blob, dtype=torch.uint8).clone().to(ents[0][5].device)
-                self.jobs_dev[dtype] = (table, len(ents), first, ents)
-            self.dirty = False
-            self.generation += 1
-        if not launch:
-            return
-        for dtype, (table, n, blocks, ents) in self.jobs_dev.items():
-            live = [ent[0]() for ent in ents]          # strong references for the duration of the launch
-            call("miseg_pack_conv3x3_weights_multi", _stream(), _DT[dtype], _ptr(table), n, blocks)
-            for ent, w in zip(ents, live):
-                ent[6], ent[7] = w._version, self.epoch
-        self.packed_epoch = self.epoch
-
-
-PACK_CACHE = _PackCache()
-
-
-def _pack(weight: Tensor, dtype, kind: int, ci_begin: int = 0, ci_count: int = 0, cin: Optional[int] = None) -> Tensor:
-    if not kind:
-        ci_begin, ci_count = 0, weight.shape[1]
-        if cin is not None and cin != weight.shape[1]:
-            return PACK_CACHE.get(weight, dtype, weight.shape[1] << 8, 0, int(cin), cin=int(cin))
-    return PACK_CACHE.get(weight, dtype, kind, int(ci_begin), int(ci_count))
+def _forward_plan(training: bool, stem_ok: bool, counter_ok: bool, use_acc: bool, acc_supported: bool, io, acc_words: int):
+    """-> (path, stem, acc): the statistics path, whether the stem kernels serve it, and the accumulator claimed from the step block.
+      1. not training                                        eval:    stem_fwd | conv3x3_fwd; bn_eval_coeffs; bn_relu_fwd
+      2. ``counter_ok`` (SYNC_COUNTERS.enabled and fusable)  counter: conv3x3_bn_fwd; bn_relu_fwd
+      3. ``use_acc`` and (stem or fwd_acc_supported) and an accumulator could be had
+                                                             acc:     stem_fwd | conv3x3_fwd_acc; bn_relu_fwd_acc
+      4. otherwise                                           rows:    conv3x3_fwd + partial rows; bn_finalize; bn_relu_fwd
+    The stem kernel hands its statistics to the accumulator only, so the counter and rows paths never take it (the packed MFMA path
+    has statistics rows; the caller then materialises a described stem operand).  ``io`` is the current step block or None: its
+    ``acc64`` claims room and is called at most once, only when row 3 is otherwise reached; it returns None when the block has no room
+    left (-> rows).  Without a step block (stand-alone use of the layer) row 3 holds and ``acc`` is None: the caller zero-fills one.
+    use_acc: 1 (default), the forward statistics leave the convolution as fixed-point atomic adds and the apply kernel finishes them
+    itself (miseg_conv3x3_fwd_acc / miseg_bn_relu_fwd_acc): 22 launches fewer per step.  0: one partial row per block + miseg_bn_finalize.
+    stem_ok: the stem (one image channel) through its own pixel-per-thread kernels reading the fp32 image, instead of the streaming
+    MFMA convolution and the tiled weight gradient on a padded channel vector: the kernels themselves are on a par (50 vs 50 us forward,
+    52 + 7 vs 59 + 10 us weight gradient -- the step's last kernel), the padded operand's 15 us launch becomes 4: -0.02 ms per step."""
+    if not training:
+        return _EVAL, stem_ok, None
+    if counter_ok:
+        return _COUNTER, False, None
+    if use_acc and (stem_ok or acc_supported):
+        if io is None:
+            return _ACC, stem_ok, None
+        acc = io.acc64(acc_words)
+        if acc is not None:
+            return _ACC, stem_ok, acc
+    return _ROWS, False, None
 
 
 class _ConvBNReLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0: Tensor, x1: Optional[Tensor], weight: Tensor, gamma: Tensor, beta: Tensor, running_mean: Tensor,
-                running_var: Tensor, nbt: Tensor, training: bool, ups0: int, ups1: int, want_pool: bool, rec: Optional[_BnRec] = None,
-                rec0: Optional[_BnRec] = None, rec1: Optional[_BnRec] = None, sink: Optional[_GradSink] = None):
+                running_var: Tensor, nbt: Tensor, cfg: tuple):
+        training, ups0, ups1, want_pool, rec, rec0, rec1, sink = cfg       # the values that are not tensors (conv_bn_relu)
         _need_gpu(x0, x1, weight)
         ctx.stem_sink = getattr(x0, "_miseg_stem_sink", None)      # stem_input's: the image itself wants a gradient
         ctx.data_only = _data_grad_only
@@ -430,56 +332,50 @@ class _ConvBNReLU(torch.autograd.Function):
         weight = weight.contiguous().float()
         # the stem (one image channel, padded to a channel vector): its own kernels, no matrix cores (miseg_conv3x3_stem_fwd / _wgrad)
         image = getattr(x0, "_miseg_stem_f32", None)       # stem_input's descriptor: x0 itself is uninitialised
-        stem = bool(_STEM_KERNELS and x1 is None and not ups0 and weight.shape[1] == 1 and c0 > 1 and w <= _STEM_MAX_W and
-                    query("miseg_conv3x3_stem_supported", _DT[dtype], 1, c0, cout))
+        stem_ok = bool(_STEM_KERNELS and x1 is None and not ups0 and weight.shape[1] == 1 and c0 > 1 and w <= _STEM_MAX_W and
+                       query("miseg_conv3x3_stem_supported", _DT[dtype], 1, c0, cout))
+        counter_ok = bool(training and SYNC_COUNTERS.enabled and query("miseg_conv3x3_bn_fwd_fusable", _DT[dtype], c0 + c1, n, h, w, cout))
+        acc_supported = bool(training and query("miseg_conv3x3_fwd_acc_supported", _DT[dtype], c0 + c1, n, h, w, cout))
+        path, stem, acc = _forward_plan(training, stem_ok, counter_ok, use_acc, acc_supported, stepio.current(), 2 * cout + 2)   # sums + misfit count
         packed = None if stem else _pack(weight, dtype, 0, cin=c0 + c1)
-        raw = empty_nhwc(n, cout, h, w, dtype, dev)
-        saved = torch.empty(4 * cout, dtype=torch.float32, device=dev)
-        counter = SYNC_COUNTERS.take(dev) if training and query("miseg_conv3x3_bn_fwd_fusable", _DT[dtype], c0 + c1, n, h, w, cout) else None
-        acc = None
-        if stem and training and (counter is not None or not use_acc):
-            stem, packed = False, _pack(weight, dtype, 0, cin=c0 + c1)       # (the stem kernel hands its statistics to the accumulator only)
-        if training and counter is None and use_acc and (stem or query("miseg_conv3x3_fwd_acc_supported", _DT[dtype], c0 + c1, n, h, w, cout)):
-            # the statistics leave the convolution as fixed-point atomic adds into one [2 C] accumulator that the step block's upload
-            # zeroed; the apply kernel turns them into coefficients itself: no partial rows, no finalize launch
-            io = stepio.current()
-            # (inside an iteration whose block has no room left: the row-per-block path below; stand-alone use of the layer: a zero fill)
-            acc = io.acc64(2 * cout + 2) if io is not None else torch.zeros(2 * cout + 2, dtype=torch.int64, device=dev)   # sums + misfit count
-            if stem and acc is None:        # no room left: the stem kernel has no statistics rows, the packed MFMA path has
-                stem, packed = False, _pack(weight, dtype, 0, cin=c0 + c1)
         if image is not None and not stem:                                  # the MFMA path after all: materialise the padded operand
             call("miseg_cast_pad", _stream(), _ptr(image), n * h * w, 1, _DT[dtype], _ptr(x0), c0)
             image = None
-        if training and acc is None:       # rows of the statistics matrix: one per block of the kernel that will serve this shape
-            parts = query("miseg_conv3x3_stats_parts", _DT[dtype], c0 + c1, n, h, w) if counter is not None else \
-                query("miseg_conv3x3_fwd_parts", _DT[dtype], c0 + c1, n, h, w, cout)
-            stats = torch.empty(parts * 2 * cout, dtype=torch.float32, device=dev)
-        else:
-            parts, stats = 0, None
+        raw = empty_nhwc(n, cout, h, w, dtype, dev)
+        saved = torch.empty(4 * cout, dtype=torch.float32, device=dev)
+        if path == _ACC and acc is None:
+            # the statistics leave the convolution as fixed-point atomic adds into one [2 C] accumulator that the step block's upload
+            # zeroed; the apply kernel turns them into coefficients itself: no partial rows, no finalize launch
+            # (stand-alone use of the layer: a zero fill)
+            acc = torch.zeros(2 * cout + 2, dtype=torch.int64, device=dev)
         es = x0.element_size()
         work = (18.0 * (c0 + c1) * cout * n * h * w, float(es) * n * h * w * (c0 / (4 ** ups0) + c1 / (4 ** ups1) + cout))
-        if stem:
+        if stem:                      # (the eval and acc paths only)
             call("miseg_conv3x3_stem_fwd", _stream(), _DT[dtype], _ptr(image if image is not None else x0), int(image is not None), 1 if image is not None else c0,
                  n, h, w, _ptr(weight), 1, cout, _ptr(raw), _ptr(acc),
                  work=(18.0 * cout * n * h * w, float(es) * n * h * w * (c0 + cout)), tag=f"conv3x3_fwd[{h}x{w},{c0 + c1}->{cout}]")
-        elif acc is not None:
+        elif path == _ACC:
             call("miseg_conv3x3_fwd_acc", _stream(), _DT[dtype], _ptr(x0), c0, ups0, _ptr(x1), c1, ups1, n, h, w, _ptr(packed), cout, _ptr(raw),
                  _ptr(acc), work=work, tag=f"conv3x3_fwd[{h}x{w},{c0 + c1}->{cout}]")
-        elif counter is not None:     # the conv's last block turns the partial sums into `saved` / the running statistics itself
+        elif path == _COUNTER:        # the conv's last block turns the partial sums into `saved` / the running statistics itself
+            # rows of the statistics matrix: one per block of the kernel that will serve this shape
+            stats = torch.empty(query("miseg_conv3x3_stats_parts", _DT[dtype], c0 + c1, n, h, w) * 2 * cout, dtype=torch.float32, device=dev)
             call("miseg_conv3x3_bn_fwd", _stream(), _DT[dtype], _ptr(x0), c0, ups0, _ptr(x1), c1, ups1, n, h, w, _ptr(packed), cout, _ptr(raw),
                  _ptr(stats), _ptr(gamma), _ptr(beta), BN_EPS, BN_MOMENTUM, _ptr(running_mean), _ptr(running_var), _ptr(nbt), _ptr(saved),
-                 _ptr(counter), work=work, tag=f"conv3x3_fwd[{h}x{w},{c0 + c1}->{cout}]")
-        else:
+                 _ptr(SYNC_COUNTERS.take(dev)), work=work, tag=f"conv3x3_fwd[{h}x{w},{c0 + c1}->{cout}]")
+        else:                         # rows: one partial row per block of the kernel that will serve this shape; eval: no statistics
+            parts = query("miseg_conv3x3_fwd_parts", _DT[dtype], c0 + c1, n, h, w, cout) if path == _ROWS else 0
+            stats = torch.empty(parts * 2 * cout, dtype=torch.float32, device=dev) if path == _ROWS else None
             call("miseg_conv3x3_fwd", _stream(), _DT[dtype], _ptr(x0), c0, ups0, _ptr(x1), c1, ups1, n, h, w, _ptr(packed), cout, _ptr(raw),
                  _ptr(stats), work=work, tag=f"conv3x3_fwd[{h}x{w},{c0 + c1}->{cout}]")
-        if training and counter is None and acc is None:
+        if path == _ROWS:
             call("miseg_bn_finalize", _stream(), _ptr(stats), parts, cout, n * h * w, _ptr(gamma), _ptr(beta), BN_EPS, BN_MOMENTUM,
                  _ptr(running_mean), _ptr(running_var), _ptr(nbt), _ptr(saved))
-        elif not training:
+        elif path == _EVAL:
             call("miseg_bn_eval_coeffs", _stream(), cout, _ptr(gamma), _ptr(beta), BN_EPS, _ptr(running_mean), _ptr(running_var), _ptr(saved))
         y = empty_nhwc(n, cout, h, w, dtype, dev)
         pooled = empty_nhwc(n, cout, h // 2, w // 2, dtype, dev) if want_pool else None
-        if acc is not None:
+        if path == _ACC:
             call("miseg_bn_relu_fwd_acc", _stream(), _DT[dtype], _ptr(raw), n, h, w, cout, _ptr(acc), _ptr(gamma), _ptr(beta), BN_EPS, BN_MOMENTUM,
                  _ptr(running_mean), _ptr(running_var), _ptr(nbt), _ptr(saved), _ptr(y), _ptr(pooled),
                  work=(0.0, float(es) * n * h * w * cout * (2.25 if want_pool else 2.0)), tag=f"bn_relu_fwd[{h}x{w},{cout}]")
@@ -505,7 +401,7 @@ class _ConvBNReLU(torch.autograd.Function):
         dtype, dev = raw.dtype, raw.device
         extras = ctx.sink.take() if ctx.sink is not None else []
         if gy is None and gpool is None and not extras:
-            return (None,) * 16
+            return _grads()
         cur = torch.cuda.current_stream(dev)
         for g2, _, _, st2 in extras:
             wait_stream(cur, st2)             # (autograd would have made the same wait before adding the two gradients)
@@ -517,7 +413,7 @@ class _ConvBNReLU(torch.autograd.Function):
             gy = gy.clone() if gy is not None else torch.zeros((n, cout, h, w), dtype=dtype, device=dev, memory_format=torch.channels_last)
             for g2, a, b, _ in extras:
                 gy[a:b] += g2.to(dtype)
-        rec, rec0, rec1 = ctx.recs
+        rec = ctx.recs[0]
         ext_parts, ext_nparts = rec.take(gy) if rec is not None else (None, 0)
         stem_grad = bool(ctx.needs_input_grad[0] and weight.shape[1] < c0)     # the gradient of the image behind a padded stem operand
         if _FUSE_BN_BWD and not want_pool and gpool is None and gy is not None and not stem_grad and _dgrads_fusable(ctx, dtype):
@@ -525,34 +421,29 @@ class _ConvBNReLU(torch.autograd.Function):
         gy = None if gy is None else as_nhwc(gy.to(dtype))
         gpool = None if gpool is None else as_nhwc(gpool.to(dtype))
         graw = empty_nhwc(n, cout, h, w, dtype, dev)
-        pw, pg, pb = ctx.param_refs
-        # written in place when the flat gradient buffer has an open slot -- only for a parameter whose gradient is wanted: a
-        # data-gradient-only pass (data_grad_only) neither claims nor writes a slot, its sums land in scratch and are dropped
-        want_g, want_b, want_w = (ctx.needs_input_grad[i] and not ctx.data_only for i in (3, 4, 2))
-        ggamma, gbeta = grad_slot(pg) if want_g else None, grad_slot(pb) if want_b else None
-        if ggamma is None:
-            ggamma = torch.empty(cout, dtype=torch.float32, device=dev)
-        if gbeta is None:
-            gbeta = torch.empty(cout, dtype=torch.float32, device=dev)
+        want_w, want_g, want_b, ggamma, gbeta = _param_grads(ctx, cout, dev)
         ws = _ws(query("miseg_bn_bwd_ws_bytes", n, h, w, cout), dev)
+        # ---- BatchNorm backward: one decision, one launch
+        use_ext = ext_parts is not None and not extras and gpool is None and gy is not None and not want_pool and dtype != torch.float16
         bacc = None
-        if _BN_ACC_BWD and not SYNC_COUNTERS.enabled and query("miseg_bn_relu_bwd_acc_supported", _DT[dtype], n, h, w, cout):
+        # _BN_ACC_BWD: the backward's sums through two fixed-point tiers (miseg_bn_relu_bwd_dual_acc).  Built and measured, OFF: the
+        # reduce kernel's blocks all finish together, so their atomics arrive as one burst on a few lines (+8 us per launch) and the
+        # apply prologue costs 5 us -- more than the finalize launch they replace (6 us + a launch boundary).  DESIGN.md section 10.
+        if not use_ext and _BN_ACC_BWD and not SYNC_COUNTERS.enabled and query("miseg_bn_relu_bwd_acc_supported", _DT[dtype], n, h, w, cout):
             # the reduce kernel adds its sums into a zeroed two-tier fixed-point accumulator, the apply kernel finishes them: no finalize launch
             io = stepio.current()
             bacc = io.acc64(4 * cout + 2) if io is not None else torch.zeros(4 * cout + 2, dtype=torch.int64, device=dev)   # (None: block full -> finalize path)
-        if ext_parts is not None and not extras and gpool is None and gy is not None and not want_pool and dtype != torch.float16:
+        g2, n0, n1 = (as_nhwc(extra[0]), extra[1], extra[2]) if extra is not None else (None, 0, 0)
+        if use_ext:
             # the data-gradient kernel that wrote gy has summed dz and dz * xhat per block in its epilogue: finalize + apply only
             call("miseg_bn_relu_bwd_ext", _stream(), _DT[dtype], _ptr(raw), _ptr(gy), n, h, w, cout, _ptr(gamma), _ptr(saved), int(training),
                  _ptr(graw), _ptr(ggamma), _ptr(gbeta), _ptr(ext_parts), ext_nparts, _ptr(ws), ws.numel(),
                  work=(0.0, float(raw.element_size()) * n * h * w * cout * 3.0), tag=f"bn_relu_bwd[{h}x{w},{cout}]")
         elif bacc is not None:
-            g2, n0, n1 = (as_nhwc(extra[0]), extra[1], extra[2]) if extra is not None else (None, 0, 0)
             call("miseg_bn_relu_bwd_dual_acc", _stream(), _DT[dtype], _ptr(raw), _ptr(gy), _ptr(gpool), _ptr(g2), n0, n1, n, h, w, cout, _ptr(gamma),
                  _ptr(saved), int(training), _ptr(graw), _ptr(ggamma), _ptr(gbeta), _ptr(ws), ws.numel(), _ptr(bacc),
                  work=(0.0, float(raw.element_size()) * n * h * w * cout * 5.0), tag=f"bn_relu_bwd[{h}x{w},{cout}]")
         elif extra is not None:
-            g2, n0, n1, _ = extra
-            g2 = as_nhwc(g2)
             call("miseg_bn_relu_bwd_dual", _stream(), _DT[dtype], _ptr(raw), _ptr(gy), _ptr(gpool), _ptr(g2), n0, n1, n, h, w, cout, _ptr(gamma),
                  _ptr(saved), int(training), _ptr(graw), _ptr(ggamma), _ptr(gbeta), _ptr(ws), ws.numel(),
                  work=(0.0, float(raw.element_size()) * n * h * w * cout * 5.0), tag=f"bn_relu_bwd[{h}x{w},{cout}]")
@@ -562,36 +453,12 @@ class _ConvBNReLU(torch.autograd.Function):
                  work=(0.0, float(raw.element_size()) * n * h * w * cout * 5.0), tag=f"bn_relu_bwd[{h}x{w},{cout}]")
         gw = None
         if want_w:
-            gw = grad_slot(pw)
-            side = None
-            if gw is None:
-                gw = torch.empty_like(weight)
-                _second_user_waits(pw, dev)
-            elif _WGRAD_SIDE and (_GRAPH_STREAMS or not torch.cuda.is_current_stream_capturing()):
-                side = wgrad_stream(dev)      # only when the result lands in the flat buffer: nothing on this stream touches it again
-            cur = torch.cuda.current_stream(dev)
-            if side is not None:
-                if not _wgrad_dirty:          # first side-stream wgrad of this backward pass: join when the pass ends, so that
-                    # param.grad (which already aliases the flat slot) is safe to touch from the main stream as soon as
-                    # backward() returns -- gradient accumulation, clip_grad_norm_, inspection -- not only after collect()
-                    torch.autograd.Variable._execution_engine.queue_callback(join_wgrad_streams)
-                wait_stream(side, cur)        # graw is produced above
-                for t in (graw, x0, x1, getattr(ctx, "image", None)):      # keep their memory from being recycled under the side stream
-                    keep(t, side)
-                _wgrad_dirty.add(dev)
-            # launched on the side stream by HANDLE (entering the `torch.cuda.stream` context costs 15-20 us of host time, 22 times per
-            # backward pass); the workspace comes from the current stream's pool and is handed to the side stream like the operands
             stem_wg = bool(ctx.stem and not _FUSE_BN_BWD)
-            ws2 = _ws(query("miseg_conv3x3_stem_wgrad_ws_bytes", cout) if stem_wg else query("miseg_conv3x3_wgrad_ws_bytes", n, h, w, c0 + c1, cout), dev)
             # the stem's weight has fewer input channels than the channel vector its activation was padded to: the kernel computes the
             # padded gradient, a slice of it is the parameter's
-            gw_full = gw if (weight.shape[1] == c0 + c1 or stem_wg) else torch.empty((cout, c0 + c1, 3, 3), dtype=torch.float32, device=dev)
-            if side is not None:
-                keep(ws2, side)
-                if gw_full is not gw:
-                    keep(gw_full, side)
+            padded = weight.shape[1] != c0 + c1 and not stem_wg
 
-            def launch(stream_handle):
+            def launch(stream_handle, gw, gw_full, ws2):
                 if stem_wg:      # the last kernel of the backward pass: a pixel-per-thread kernel, gw [cout][1][3][3] written directly
                     img = ctx.image
                     call("miseg_conv3x3_stem_wgrad", stream_handle, _DT[dtype], _ptr(img if img is not None else x0), int(img is not None),
@@ -603,97 +470,18 @@ class _ConvBNReLU(torch.autograd.Function):
                      tag=f"conv3x3_wgrad[{h}x{w},{c0 + c1}->{cout}]")
                 if gw_full is not gw:
                     call("miseg_conv3x3_wgrad_slice", stream_handle, _ptr(gw_full), cout, c0 + c1, weight.shape[1], _ptr(gw))
-            if side is None:
-                launch(_stream())
-            elif _cabi.TIMER is not None:       # the per-kernel timer records its events on torch's current stream
-                with torch.cuda.stream(side):
-                    launch(_stream())
-            else:
-                launch(side.cuda_stream)
-        grads = [None, None]
-        if _DUAL_DGRAD and x1 is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not ups0 and not ups1 and \
-                c0 % 16 == 0 and c1 % 4 == 0 and not _GradJoin.enabled and not (_FUSE_BN_BWD and _FUSE_BN_RED) and not _RED_ONLY:
-            # concat of two full-resolution sources: both data gradients in ONE launch (graw read once, twice the blocks)
-            packed = _pack(weight, dtype, 1, 0, c0 + c1)
-            g0, g1 = empty_nhwc(n, c0, h, w, dtype, dev), empty_nhwc(n, c1, h, w, dtype, dev)
-            call("miseg_conv3x3_dgrad_dual", _stream(), _DT[dtype], _ptr(graw), cout, n, h, w, _ptr(packed), c0, _ptr(g0), c1, _ptr(g1),
-                 work=(18.0 * (c0 + c1) * cout * n * h * w, float(raw.element_size()) * n * h * w * (c0 + c1 + cout)),
-                 tag=f"conv3x3_dgrad[{h}x{w},{cout}->{c0}+{c1}]")
-            return g0, g1, gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
-        if stem_grad:
-            cin = weight.shape[1]
-            sink = ctx.stem_sink
-            if sink is not None and _STEM_DGRAD and cin == 1 and query("miseg_conv3x3_stem_dgrad_supported", _DT[dtype], cout, w):
-                # one image channel: the stem's own kernel writes the fp32 image gradient; it reaches the image through the sink
-                sink.grad = stem_dgrad(graw, weight)
-                return None, None, gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
-            # the generic path; the padded channels' gradients are computed and dropped (stem_input's backward keeps the real ones)
-            gfull = stem_dgrad_generic(graw, weight, c0)
-            return gfull, None, gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
-        for s, (cb, cs, ups, xs) in enumerate(((0, c0, ups0, x0), (c0, c1, ups1, x1))):
-            if xs is None or not ctx.needs_input_grad[s]:
-                continue
-            packed = _pack(weight, dtype, 1, cb, cs)
-            if ups and _FUSE_UPS_DGRAD and query("miseg_conv3x3_fwd_sumpool_supported", _DT[dtype], cout, n, h, w, cs):
-                # the source was read through the x2 upsample: its gradient is the 2x2 sum-pool of the data gradient -- pooled in the
-                # convolution's epilogue, the full-resolution gradient (4x the bytes) never exists
-                joined = _GradJoin.take(xs) if query("miseg_conv3x3_fwd_sumpool_acc_supported", _DT[dtype], cout, n, h, w) else None
-                if joined is not None:
-                    # the source is also a local-MI tap and its head's backward has already written its gradient: add ours into it
-                    gsum, written, writer = joined
-                    cur_s = torch.cuda.current_stream(dev)
-                    cur_s.wait_event(written)
-                    gsum.record_stream(cur_s)
-                    call("miseg_conv3x3_fwd_sumpool_acc", _stream(), _DT[dtype], _ptr(graw), cout, n, h, w, _ptr(packed), cs, _ptr(gsum),
-                         work=(18.0 * cs * cout * n * h * w, float(raw.element_size()) * n * h * w * (cs / 2 + cout)),
-                         tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
-                    if writer != cur_s:
-                        done = torch.cuda.Event()
-                        done.record(cur_s)
-                        writer.wait_event(done)
-                    grads[s] = None
-                    continue
-                glow = empty_nhwc(n, cs, h // 2, w // 2, dtype, dev)
-                call("miseg_conv3x3_fwd_sumpool", _stream(), _DT[dtype], _ptr(graw), cout, n, h, w, _ptr(packed), cs, _ptr(glow),
-                     work=(18.0 * cs * cout * n * h * w, float(raw.element_size()) * n * h * w * (cs / 4 + cout)),
-                     tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
-                _GradJoin.offer(xs, glow)      # if the source is a tap whose head backward has yet to run, it adds into this tensor
-                grads[s] = glow
-                continue
-            gfull = empty_nhwc(n, cs, h, w, dtype, dev)
-            src_rec = (rec0, rec1)[s]
-            red = _red_target(src_rec, ups, dtype, cout, n, h, w, cs)
-            if red is not None:      # the source is a BatchNorm layer read at full resolution: its backward sums in this launch's epilogue
-                parts, nparts = red
-                call("miseg_conv3x3_dgrad_bn", _stream(), _DT[dtype], _ptr(graw), None, None, cout, n, h, w, _ptr(packed), cs, _ptr(gfull), 0,
-                     _ptr(src_rec.raw), _ptr(src_rec.saved), _ptr(parts),
-                     work=(18.0 * cs * cout * n * h * w, float(raw.element_size()) * n * h * w * (2 * cs + cout)), tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
-                src_rec.offer(gfull, parts, nparts)
-                grads[s] = gfull
-                continue
-            call("miseg_conv3x3_fwd", _stream(), _DT[dtype], _ptr(graw), cout, 0, None, 0, 0, n, h, w, _ptr(packed), cs, _ptr(gfull), None,
-                 work=(18.0 * cs * cout * n * h * w, float(raw.element_size()) * n * h * w * (cs + cout)), tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
-            if ups:
-                glow = empty_nhwc(n, cs, h // 2, w // 2, dtype, dev)
-                call("miseg_sumpool2x2", _stream(), _DT[dtype], _ptr(gfull), n, h, w, cs, _ptr(glow), 0)
-                gfull = glow
-            grads[s] = gfull
-        return grads[0], grads[1], gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
+            gw = _wgrad_fork(ctx.param_refs[0], weight, dev, (graw, x0, x1, ctx.image), launch, c0 + c1 if padded else None,
+                             query("miseg_conv3x3_stem_wgrad_ws_bytes", cout) if stem_wg else query("miseg_conv3x3_wgrad_ws_bytes", n, h, w, c0 + c1, cout))
+        g0, g1 = _data_grads(ctx, graw, x0, x1, weight, stem_grad)
+        return _grads(g0, g1, gw, ggamma if want_g else None, gbeta if want_b else None)
 
     @staticmethod
     def _backward_fused(ctx, gy_in: Tensor, ext_parts: Optional[Tensor], ext_nparts: int):
         x0, x1, weight, gamma, raw, y, saved = ctx.saved_tensors
         training, ups0, ups1, want_pool, c0, c1, n, h, w, cout = ctx.cfg
-        rec, rec0, rec1 = ctx.recs
         dtype, dev, es = raw.dtype, raw.device, raw.element_size()
         gy = as_nhwc(gy_in.to(dtype))
-        pw, pg, pb = ctx.param_refs
-        want_g, want_b, want_w = (ctx.needs_input_grad[i] and not ctx.data_only for i in (3, 4, 2))     # (see backward)
-        ggamma, gbeta = grad_slot(pg) if want_g else None, grad_slot(pb) if want_b else None
-        if ggamma is None:
-            ggamma = torch.empty(cout, dtype=torch.float32, device=dev)
-        if gbeta is None:
-            gbeta = torch.empty(cout, dtype=torch.float32, device=dev)
+        want_w, want_g, want_b, ggamma, gbeta = _param_grads(ctx, cout, dev)
         coef = torch.empty(6 * cout, dtype=torch.float32, device=dev)
         if ext_parts is not None:       # the consumer's data-gradient kernel already summed dz and dz * xhat per block: finalize only
             call("miseg_bn_relu_bwd_stats", _stream(), _DT[dtype], None, None, n, h, w, cout, _ptr(gamma), _ptr(saved), int(training), _ptr(coef),
@@ -705,56 +493,186 @@ class _ConvBNReLU(torch.autograd.Function):
                  work=(0.0, float(es) * n * h * w * cout * 2.0), tag=f"bn_relu_bwd[{h}x{w},{cout}]")
         gw = None
         if want_w:
-            gw = grad_slot(pw)
-            side = None
-            if gw is None:
-                gw = torch.empty_like(weight)
-                _second_user_waits(pw, dev)
-            elif _WGRAD_SIDE and (_GRAPH_STREAMS or not torch.cuda.is_current_stream_capturing()):
-                side = wgrad_stream(dev)
-            cur = torch.cuda.current_stream(dev)
-            if side is not None:
-                if not _wgrad_dirty:
-                    torch.autograd.Variable._execution_engine.queue_callback(join_wgrad_streams)
-                wait_stream(side, cur)        # coef is produced above
-                for t in (raw, gy, coef, x0, x1):
-                    keep(t, side)
-                _wgrad_dirty.add(dev)
-            with torch.cuda.stream(side if side is not None else cur):
-                ws2 = _ws(query("miseg_conv3x3_wgrad_ws_bytes", n, h, w, c0 + c1, cout), dev)
-                call("miseg_conv3x3_wgrad_bn", _stream(), _DT[dtype], _ptr(x0), c0, ups0, _ptr(x1), c1, ups1, n, h, w, _ptr(raw), _ptr(gy), _ptr(coef),
+            def launch(stream_handle, gw, gw_full, ws2):
+                call("miseg_conv3x3_wgrad_bn", stream_handle, _DT[dtype], _ptr(x0), c0, ups0, _ptr(x1), c1, ups1, n, h, w, _ptr(raw), _ptr(gy), _ptr(coef),
                      cout, _ptr(gw), _ptr(ws2), ws2.numel(),
                      work=(18.0 * (c0 + c1) * cout * n * h * w, float(es) * n * h * w * (c0 + c1 + 2 * cout)), tag=f"conv3x3_wgrad[{h}x{w},{c0 + c1}->{cout}]")
-        grads = [None, None]
-        for s, (cb, cs, ups, xs, src_rec) in enumerate(((0, c0, ups0, x0, rec0), (c0, c1, ups1, x1, rec1))):
-            if xs is None or not ctx.needs_input_grad[s]:
-                continue
-            packed = _pack(weight, dtype, 1, cb, cs)
-            flops = 18.0 * cs * cout * n * h * w
-            pooled = bool(ups) and bool(query("miseg_conv3x3_dgrad_bn_supported", _DT[dtype], cout, n, h, w, cs, 1))
-            if pooled:
-                glow = empty_nhwc(n, cs, h // 2, w // 2, dtype, dev)
-                call("miseg_conv3x3_dgrad_bn", _stream(), _DT[dtype], _ptr(raw), _ptr(gy), _ptr(coef), cout, n, h, w, _ptr(packed), cs, _ptr(glow), 1,
-                     None, None, None, work=(flops, float(es) * n * h * w * (cs / 4 + 2 * cout)), tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
-                grads[s] = glow
-                continue
-            gfull = empty_nhwc(n, cs, h, w, dtype, dev)
-            red = _red_target(src_rec, ups, dtype, cout, n, h, w, cs)
-            if red is not None:
-                parts, nparts = red
-                call("miseg_conv3x3_dgrad_bn", _stream(), _DT[dtype], _ptr(raw), _ptr(gy), _ptr(coef), cout, n, h, w, _ptr(packed), cs, _ptr(gfull), 0,
-                     _ptr(src_rec.raw), _ptr(src_rec.saved), _ptr(parts), work=(flops, float(es) * n * h * w * (2 * cs + 2 * cout)),
-                     tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
-                src_rec.offer(gfull, parts, nparts)
-            else:
-                call("miseg_conv3x3_dgrad_bn", _stream(), _DT[dtype], _ptr(raw), _ptr(gy), _ptr(coef), cout, n, h, w, _ptr(packed), cs, _ptr(gfull), 0,
-                     None, None, None, work=(flops, float(es) * n * h * w * (cs + 2 * cout)), tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
-            if ups:
-                glow = empty_nhwc(n, cs, h // 2, w // 2, dtype, dev)
-                call("miseg_sumpool2x2", _stream(), _DT[dtype], _ptr(gfull), n, h, w, cs, _ptr(glow), 0)
-                gfull = glow
-            grads[s] = gfull
-        return grads[0], grads[1], gw, ggamma if want_g else None, gbeta if want_b else None, None, None, None, None, None, None, None, None, None, None, None
+            gw = _wgrad_fork(ctx.param_refs[0], weight, dev, (raw, gy, coef, x0, x1), launch, None, query("miseg_conv3x3_wgrad_ws_bytes", n, h, w, c0 + c1, cout))
+        g0, g1 = _source_grads(ctx, x0, x1, _dgrad_folded, raw, gy, coef, weight)
+        return _grads(g0, g1, gw, ggamma if want_g else None, gbeta if want_b else None)
+
+
+def _grads(g0=None, g1=None, gw=None, ggamma=None, gbeta=None):
+    """What a backward of ``_ConvBNReLU`` returns: the five gradients, and None for every other argument of ``forward``."""
+    return (g0, g1, gw, ggamma, gbeta) + _NO_GRADS
+
+
+_NO_GRADS = (None,) * (_ConvBNReLU.forward.__code__.co_argcount - 1 - 5)      # (ctx; x0, x1, weight, gamma, beta)
+
+
+def _param_grads(ctx, cout: int, dev):
+    """-> (want_w, want_g, want_b, ggamma, gbeta): which parameter gradients the backward delivers, and where gamma's and beta's sums
+    go.  Written in place when the flat gradient buffer has an open slot -- only for a parameter whose gradient is wanted: a
+    data-gradient-only pass (data_grad_only) neither claims nor writes a slot, its sums land in scratch and are dropped."""
+    _, pg, pb = ctx.param_refs
+    want_g, want_b, want_w = (ctx.needs_input_grad[i] and not ctx.data_only for i in (3, 4, 2))
+    ggamma, gbeta = grad_slot(pg) if want_g else None, grad_slot(pb) if want_b else None
+    if ggamma is None:
+        ggamma = torch.empty(cout, dtype=torch.float32, device=dev)
+    if gbeta is None:
+        gbeta = torch.empty(cout, dtype=torch.float32, device=dev)
+    return want_w, want_g, want_b, ggamma, gbeta
+
+
+def _wgrad_fork(pw, weight: Tensor, dev, operands, launch, padded_cin: Optional[int], ws_bytes: int) -> Tensor:
+    """The weight gradient of one layer, on the side stream when its result lands in the flat buffer (nothing on this stream touches it
+    again): ``launch(stream_handle, gw, gw_full, ws)`` issues the kernels that read ``operands``; -> ``gw``.  ``padded_cin``: the kernel
+    writes a gradient of that many input channels into ``gw_full``, a scratch tensor (None: ``gw_full`` is ``gw``)."""
+    gw = grad_slot(pw)
+    side = None
+    if gw is None:
+        gw = torch.empty_like(weight)
+        _second_user_waits(pw, dev)
+    elif _WGRAD_SIDE and side_streams_allowed():
+        side = wgrad_stream(dev)
+    # the workspace comes from the current stream's pool and is handed to the side stream like the operands
+    ws = _ws(ws_bytes, dev)
+    gw_full = gw if padded_cin is None else torch.empty((weight.shape[0], padded_cin, 3, 3), dtype=torch.float32, device=dev)
+    if side is None:
+        launch(_stream(), gw, gw_full, ws)
+        return gw
+    if not _wgrad_dirty:          # first side-stream wgrad of this backward pass: join when the pass ends, so that
+        # param.grad (which already aliases the flat slot) is safe to touch from the main stream as soon as
+        # backward() returns -- gradient accumulation, clip_grad_norm_, inspection -- not only after collect()
+        torch.autograd.Variable._execution_engine.queue_callback(join_wgrad_streams)
+    wait_stream(side, torch.cuda.current_stream(dev))        # the operands are produced on the current stream
+    for t in operands:            # keep their memory from being recycled under the side stream
+        keep(t, side)
+    keep(ws, side)
+    if gw_full is not gw:
+        keep(gw_full, side)
+    _wgrad_dirty.add(dev)
+    # launched on the side stream by HANDLE (entering the `torch.cuda.stream` context costs 15-20 us of host time, 22 times per
+    # backward pass)
+    if _cabi.TIMER is not None:       # the per-kernel timer records its events on torch's current stream
+        with torch.cuda.stream(side):
+            launch(_stream(), gw, gw_full, ws)
+    else:
+        launch(side.cuda_stream, gw, gw_full, ws)
+    return gw
+
+
+def _data_grads(ctx, graw: Tensor, x0: Tensor, x1: Optional[Tensor], weight: Tensor, stem_grad: bool):
+    """The data gradients (g0, g1) of the three-pass backward from ``graw``: both sources of a concat in one launch, the image behind a
+    padded stem operand, or one launch per source (``_dgrad_plain``)."""
+    training, ups0, ups1, want_pool, c0, c1, n, h, w, cout = ctx.cfg
+    dtype, dev = graw.dtype, graw.device
+    if _DUAL_DGRAD and x1 is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not ups0 and not ups1 and \
+            c0 % 16 == 0 and c1 % 4 == 0 and not _GradJoin.enabled and not _epilogue_sums_allowed():
+        # concat of two full-resolution sources: both data gradients in ONE launch (graw read once, twice the blocks)
+        packed = _pack(weight, dtype, 1, 0, c0 + c1)
+        g0, g1 = empty_nhwc(n, c0, h, w, dtype, dev), empty_nhwc(n, c1, h, w, dtype, dev)
+        call("miseg_conv3x3_dgrad_dual", _stream(), _DT[dtype], _ptr(graw), cout, n, h, w, _ptr(packed), c0, _ptr(g0), c1, _ptr(g1),
+             work=(18.0 * (c0 + c1) * cout * n * h * w, float(graw.element_size()) * n * h * w * (c0 + c1 + cout)),
+             tag=f"conv3x3_dgrad[{h}x{w},{cout}->{c0}+{c1}]")
+        return g0, g1
+    if stem_grad:
+        sink = ctx.stem_sink
+        if sink is not None and _STEM_DGRAD and weight.shape[1] == 1 and query("miseg_conv3x3_stem_dgrad_supported", _DT[dtype], cout, w):
+            # one image channel: the stem's own kernel writes the fp32 image gradient; it reaches the image through the sink
+            sink.grad = stem_dgrad(graw, weight)
+            return None, None
+        # the generic path; the padded channels' gradients are computed and dropped (stem_input's backward keeps the real ones)
+        return stem_dgrad_generic(graw, weight, c0), None
+    return _source_grads(ctx, x0, x1, _dgrad_plain, graw, weight)
+
+
+def _source_grads(ctx, x0: Tensor, x1: Optional[Tensor], one, *operands):
+    """(g0, g1) = ``one(cfg, *operands, cb, cs, ups, xs, src_rec)`` for each source that wants a gradient: its channel range in the
+    weight, its upsampling, the source tensor and the source layer's hand-over record."""
+    training, ups0, ups1, want_pool, c0, c1, n, h, w, cout = ctx.cfg
+    rec, rec0, rec1 = ctx.recs
+    grads = [None, None]
+    for s, (cb, cs, ups, xs, src_rec) in enumerate(((0, c0, ups0, x0, rec0), (c0, c1, ups1, x1, rec1))):
+        if xs is not None and ctx.needs_input_grad[s]:
+            grads[s] = one(ctx.cfg, *operands, cb, cs, ups, xs, src_rec)
+    return grads
+
+
+def _dgrad_plain(cfg, graw: Tensor, weight: Tensor, cb: int, cs: int, ups: int, xs: Tensor, src_rec: Optional[_BnRec]) -> Optional[Tensor]:
+    """One source's data gradient from ``graw`` (the three-pass backward)."""
+    n, h, w, cout = cfg[6:10]
+    dtype, dev, es = graw.dtype, graw.device, graw.element_size()
+    packed = _pack(weight, dtype, 1, cb, cs)
+    if ups and _FUSE_UPS_DGRAD and query("miseg_conv3x3_fwd_sumpool_supported", _DT[dtype], cout, n, h, w, cs):
+        # the source was read through the x2 upsample: its gradient is the 2x2 sum-pool of the data gradient -- pooled in the
+        # convolution's epilogue, the full-resolution gradient (4x the bytes) never exists
+        joined = _GradJoin.take(xs) if query("miseg_conv3x3_fwd_sumpool_acc_supported", _DT[dtype], cout, n, h, w) else None
+        if joined is not None:
+            # the source is also a local-MI tap and its head's backward has already written its gradient: add ours into it
+            gsum, written, writer = joined
+            cur_s = torch.cuda.current_stream(dev)
+            cur_s.wait_event(written)
+            gsum.record_stream(cur_s)
+            call("miseg_conv3x3_fwd_sumpool_acc", _stream(), _DT[dtype], _ptr(graw), cout, n, h, w, _ptr(packed), cs, _ptr(gsum),
+                 work=(18.0 * cs * cout * n * h * w, float(es) * n * h * w * (cs / 2 + cout)),
+                 tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
+            if writer != cur_s:
+                done = torch.cuda.Event()
+                done.record(cur_s)
+                writer.wait_event(done)
+            return None
+        glow = empty_nhwc(n, cs, h // 2, w // 2, dtype, dev)
+        call("miseg_conv3x3_fwd_sumpool", _stream(), _DT[dtype], _ptr(graw), cout, n, h, w, _ptr(packed), cs, _ptr(glow),
+             work=(18.0 * cs * cout * n * h * w, float(es) * n * h * w * (cs / 4 + cout)),
+             tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
+        _GradJoin.offer(xs, glow)      # if the source is a tap whose head backward has yet to run, it adds into this tensor
+        return glow
+    gfull = empty_nhwc(n, cs, h, w, dtype, dev)
+    red = _red_target(src_rec, ups, dtype, cout, n, h, w, cs)
+    if red is not None:      # the source is a BatchNorm layer read at full resolution: its backward sums in this launch's epilogue
+        parts, nparts = red
+        call("miseg_conv3x3_dgrad_bn", _stream(), _DT[dtype], _ptr(graw), None, None, cout, n, h, w, _ptr(packed), cs, _ptr(gfull), 0,
+             _ptr(src_rec.raw), _ptr(src_rec.saved), _ptr(parts),
+             work=(18.0 * cs * cout * n * h * w, float(es) * n * h * w * (2 * cs + cout)), tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
+        src_rec.offer(gfull, parts, nparts)
+        return gfull
+    call("miseg_conv3x3_fwd", _stream(), _DT[dtype], _ptr(graw), cout, 0, None, 0, 0, n, h, w, _ptr(packed), cs, _ptr(gfull), None,
+         work=(18.0 * cs * cout * n * h * w, float(es) * n * h * w * (cs + cout)), tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
+    return _sumpooled(gfull, cs, n, h, w) if ups else gfull
+
+
+def _dgrad_folded(cfg, raw: Tensor, gy: Tensor, coef: Tensor, weight: Tensor, cb: int, cs: int, ups: int, xs: Tensor,
+                  src_rec: Optional[_BnRec]) -> Tensor:
+    """One source's data gradient with graw formed in the kernel's loader from ``raw``, ``gy`` and ``coef`` (the folded backward)."""
+    n, h, w, cout = cfg[6:10]
+    dtype, dev, es = raw.dtype, raw.device, raw.element_size()
+    packed = _pack(weight, dtype, 1, cb, cs)
+    flops = 18.0 * cs * cout * n * h * w
+    if ups and query("miseg_conv3x3_dgrad_bn_supported", _DT[dtype], cout, n, h, w, cs, 1):
+        glow = empty_nhwc(n, cs, h // 2, w // 2, dtype, dev)
+        call("miseg_conv3x3_dgrad_bn", _stream(), _DT[dtype], _ptr(raw), _ptr(gy), _ptr(coef), cout, n, h, w, _ptr(packed), cs, _ptr(glow), 1,
+             None, None, None, work=(flops, float(es) * n * h * w * (cs / 4 + 2 * cout)), tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
+        return glow
+    gfull = empty_nhwc(n, cs, h, w, dtype, dev)
+    red = _red_target(src_rec, ups, dtype, cout, n, h, w, cs)
+    if red is not None:
+        parts, nparts = red
+        call("miseg_conv3x3_dgrad_bn", _stream(), _DT[dtype], _ptr(raw), _ptr(gy), _ptr(coef), cout, n, h, w, _ptr(packed), cs, _ptr(gfull), 0,
+             _ptr(src_rec.raw), _ptr(src_rec.saved), _ptr(parts), work=(flops, float(es) * n * h * w * (2 * cs + 2 * cout)),
+             tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
+        src_rec.offer(gfull, parts, nparts)
+    else:
+        call("miseg_conv3x3_dgrad_bn", _stream(), _DT[dtype], _ptr(raw), _ptr(gy), _ptr(coef), cout, n, h, w, _ptr(packed), cs, _ptr(gfull), 0,
+             None, None, None, work=(flops, float(es) * n * h * w * (cs + 2 * cout)), tag=f"conv3x3_dgrad[{h}x{w},{cout}->{cs}]")
+    return _sumpooled(gfull, cs, n, h, w) if ups else gfull
+
+
+def _sumpooled(gfull: Tensor, cs: int, n: int, h: int, w: int) -> Tensor:
+    """The gradient of a source read through the x2 upsample, from its full-resolution gradient: the 2x2 sums, as a launch of their own."""
+    glow = empty_nhwc(n, cs, h // 2, w // 2, gfull.dtype, gfull.device)
+    call("miseg_sumpool2x2", _stream(), _DT[gfull.dtype], _ptr(gfull), n, h, w, cs, _ptr(glow), 0)
+    return glow
 
 
 def stem_dgrad_supported(dtype, cout: int, w: int) -> bool:
@@ -810,7 +728,7 @@ def _dgrads_fusable(ctx, dtype) -> bool:
 
 def _red_target(src_rec: Optional[_BnRec], ups: int, dtype, cout: int, n: int, h: int, w: int, cs: int):
     """(parts, nparts) if this data-gradient launch can take the source layer's BatchNorm-backward sums in its epilogue."""
-    if not ((_FUSE_BN_BWD and _FUSE_BN_RED) or _RED_ONLY) or src_rec is None or ups or src_rec.raw is None or src_rec.shape != (n, cs, h, w) or \
+    if not _epilogue_sums_allowed() or src_rec is None or ups or src_rec.raw is None or src_rec.shape != (n, cs, h, w) or \
             src_rec.raw.dtype != dtype:
         return None
     nparts = query("miseg_conv3x3_dgrad_red_parts", _DT[dtype], cout, n, h, w, cs)
@@ -822,14 +740,20 @@ def _red_target(src_rec: Optional[_BnRec], ups: int, dtype, cout: int, n: int, h
 def conv_bn_relu(x0: Tensor, x1: Optional[Tensor], weight: Tensor, gamma: Tensor, beta: Tensor, running_mean: Tensor,
                  running_var: Tensor, nbt: Tensor, training: bool, ups0: int = 0, ups1: int = 0,
                  want_pool: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
+    # BatchNorm backward folded into the convolutions around it (_FUSE_BN_BWD; layers without the fused pool): the statistics pass leaves
+    # six coefficients per channel, the data- and weight-gradient kernels form graw in their loaders (no bn_bwd_apply pass, no graw
+    # tensor), and a data-gradient launch whose output is the activation gradient of ANOTHER such layer takes that layer's statistics
+    # pass in its epilogue (no bn_relu_bwd_reduce pass there).  OFF by default (MISEG_BN_FUSE=1 turns it on): measured slower,
+    # DESIGN.md section 9.
     # the hand-over record exists only where it can be used: the opt-in fused backward, a layer without the fused pool (a pooled layer's
     # backward routes through the 2x2 windows and keeps its own reduce), a forward pass that records a graph
-    rec = _BnRec() if (((_FUSE_BN_BWD and _FUSE_BN_RED) or _RED_ONLY) and not want_pool and torch.is_grad_enabled()) else None
+    rec = _BnRec() if (_epilogue_sums_allowed() and not want_pool and torch.is_grad_enabled()) else None
     rec0 = getattr(x0, "_miseg_bn", None) if not ups0 else None
     rec1 = getattr(x1, "_miseg_bn", None) if x1 is not None and not ups1 else None
     sink = _GradSink() if torch.is_grad_enabled() and not _FUSE_BN_BWD else None
-    y, pooled = _ConvBNReLU.apply(x0, x1, weight, gamma, beta, running_mean, running_var, nbt, bool(training), int(ups0), int(ups1),
-                                  bool(want_pool), rec, rec0, rec1, sink)
+    # the values that are not tensors travel as one object, so that autograd's `apply` and `needs_input_grad` see nine arguments
+    y, pooled = _ConvBNReLU.apply(x0, x1, weight, gamma, beta, running_mean, running_var, nbt,
+                                  (bool(training), int(ups0), int(ups1), bool(want_pool), rec, rec0, rec1, sink))
     if rec is not None and rec.raw is not None:
         y._miseg_bn = rec
     if sink is not None and y.requires_grad:

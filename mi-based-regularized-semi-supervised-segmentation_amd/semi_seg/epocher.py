@@ -39,7 +39,7 @@ from deepclustering2.meters2 import (AverageValueMeter, EpochResultDict, MeterIn
 from deepclustering2.optim import get_lrs_from_optimizer
 from deepclustering2.type import T_loader, T_loss, T_optim
 from deepclustering2.utils import class2one_hot
-from miseg_amd import checks, lazy, ops, stepio, unet_ops
+from miseg_amd import checks, lazy, ops, packcache, stepio, unet_ops
 from miseg_amd.lazy import LinearLoss
 from miseg_amd.tape import keep as _keep
 from semi_seg._utils import FeatureExtractor, IICLossWrapper, KLDiceLoss, ProjectorWrapper
@@ -459,7 +459,7 @@ class TrainEpocher(_num_class_mixin, _Epocher):
             stepio.CURRENT = None
 
     def _after_replay(self) -> None:
-        unet_ops.PACK_CACHE.invalidate()       # the replay ran Adam: eager users of the weights (evaluation) must re-pack
+        packcache.PACK_CACHE.invalidate()       # the replay ran Adam: eager users of the weights (evaluation) must re-pack
 
     def _post(self, io):
         """The iteration's report (if the guarded optimiser launch has not computed it already) and the one device -> host copy."""
@@ -694,7 +694,7 @@ class IICTrainEpocher(TrainEpocher):
         if dev.type != "cuda" or os.environ.get("MISEG_IIC_STREAM", "1") != "1":
             return False
         # under hipGraph capture the fork/join (wait_stream both ways) is captured as graph dependencies
-        return os.environ.get("MISEG_GRAPH_STREAMS", "1") == "1" or not torch.cuda.is_current_stream_capturing()
+        return unet_ops.side_streams_allowed()
 
     def _side(self, dev):
         side = getattr(self, "_iic_stream", None)

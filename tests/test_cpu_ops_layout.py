@@ -1,5 +1,5 @@
 """Layout of ``miseg_amd`` on the CPU: the names ``miseg_amd.ops`` has to offer, the import order of the layers under it
-(``_cabi`` < ``_rt`` < ``stepio`` < ``tape``, ``checks``, ``gradslot``, ``lazy`` < ``unet_ops`` < the ``ops`` families), where an import may still
+(``_cabi`` < ``_rt`` < ``stepio`` < ``tape``, ``checks``, ``gradslot``, ``packcache``, ``lazy`` < ``unet_ops`` < the ``ops`` families), where an import may still
 sit inside a function, the one home of the local-MI precision, and the independence of the family modules.  Every expected name and
 every exception is a literal here."""
 import ast
@@ -32,9 +32,7 @@ SHARED = {("losses", "batch"): {"_scaled_grad", "_split_part_of"}, ("mi", "batch
 
 # (file, function, imported module) -> why the import is not at the top of the file
 LAZY_IMPORTS = {
-    ("tape.py", "_key", ".unet_ops"): "the tape key reads PACK_CACHE.generation; unet_ops imports tape (keep)",
     ("tape.py", "_key", ".ops.mi"): "the tape key reads the local-MI precision; ops is the top layer",
-    ("tape.py", "_settle", ".unet_ops"): "settles PACK_CACHE before recording; unet_ops imports tape (keep)",
 }
 
 
@@ -64,7 +62,7 @@ def test_ops_offers_every_name_the_repository_uses():
 
 def test_lower_layers_import_without_the_upper_ones():
     code = ("import sys\n"
-            "import miseg_amd._rt, miseg_amd.stepio, miseg_amd.checks\n"
+            "import miseg_amd._rt, miseg_amd.stepio, miseg_amd.checks, miseg_amd.packcache, miseg_amd.tape\n"
             "assert 'miseg_amd.ops' not in sys.modules and 'miseg_amd.unet_ops' not in sys.modules, sorted(m for m in sys.modules if m.startswith('miseg_amd'))\n"
             "import miseg_amd.unet_ops\n"
             "assert 'miseg_amd.ops' not in sys.modules, sorted(m for m in sys.modules if m.startswith('miseg_amd'))\n")

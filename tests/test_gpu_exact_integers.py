@@ -116,8 +116,8 @@ def scratch(nbytes):
 
 
 def pack(wt64, dtype, kind=0, ci_begin=0, ci_count=0, cin=None):
-    from miseg_amd import unet_ops
-    return unet_ops._pack_now(f32(wt64), dtype, kind, ci_begin, ci_count if kind else wt64.shape[1], cin=cin)
+    from miseg_amd import packcache
+    return packcache._pack_now(f32(wt64), dtype, kind, ci_begin, ci_count if kind else wt64.shape[1], cin=cin)
 
 
 def pairs(table):

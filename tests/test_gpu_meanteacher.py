@@ -239,7 +239,7 @@ def test_freeing_a_registered_network_rerecords_the_tape():
     ``PACK_CACHE.generation`` at once, the next step drops the tape (its job table named the freed weights) and a later one records
     a new tape that replays."""
     import bench
-    from miseg_amd import unet_ops
+    from miseg_amd import packcache
     from miseg_amd.flat import FlatBuffers
     ep, model, teacher, opt, upd = build("float32")
     other = th.unet("float32", 51).train()
@@ -255,10 +255,10 @@ def test_freeing_a_registered_network_rerecords_the_tape():
         drv.step()
     tp = ep._step_tape
     assert tp.handle and tp.replays == 1, (tp.handle, tp.replays, tp.disabled)
-    gen = unet_ops.PACK_CACHE.generation
+    gen = packcache.PACK_CACHE.generation
     del other, fb
     gc.collect()
-    assert unet_ops.PACK_CACHE.generation != gen
+    assert packcache.PACK_CACHE.generation != gen
     drv.step()
     assert tp.replays == 1 and not tp.handle          # released, not replayed
     for _ in range(4):

@@ -871,8 +871,8 @@ CONV = (3, 20, 36)              # exact_ref "tiled_ragged_*" / "few_tiles_*": N,
 
 
 def pack(wt, dtype, kind=0, cb=0, cs=0, cin=None):
-    from miseg_amd import unet_ops
-    p = unet_ops._pack_now(wt, dtype, kind, cb, cs if kind else wt.shape[1], cin=cin)
+    from miseg_amd import packcache
+    p = packcache._pack_now(wt, dtype, kind, cb, cs if kind else wt.shape[1], cin=cin)
     torch.cuda.synchronize()
     return p
 

@@ -408,7 +408,7 @@ def test_conv3x3_exact_properties_at_full_size(n, h, w, cin, cout, dtype):
     properties that hold EXACTLY: (a) a centre-tap identity kernel returns the input bit for bit; (b) all-ones weights on an all-ones
     input give (valid taps) x Cin at every pixel -- 9 Cin inside, 6 Cin on edges, 4 Cin in corners (zero padding, ref unet.py:15);
     (c) the pooled-output form (`miseg_conv3x3_fwd_sumpool`, where supported) gives the 2 x 2 sums of (b)."""
-    from miseg_amd import _cabi, unet_ops
+    from miseg_amd import _cabi, packcache
     from miseg_amd.ops import _DT
     dt = _DT[dtype]
     st = torch.cuda.current_stream().cuda_stream
@@ -418,13 +418,13 @@ def test_conv3x3_exact_properties_at_full_size(n, h, w, cin, cout, dtype):
         wid = torch.zeros(cout, cin, 3, 3, device=DEV)
         wid[torch.arange(cout), torch.arange(cin), 1, 1] = 1.0
         out = torch.empty_like(x)
-        _cabi.call("miseg_conv3x3_fwd", st, dt, x.data_ptr(), cin, 0, None, 0, 0, n, h, w, unet_ops._pack_now(wid, dtype, 0, 0, cin).data_ptr(), cout,
+        _cabi.call("miseg_conv3x3_fwd", st, dt, x.data_ptr(), cin, 0, None, 0, 0, n, h, w, packcache._pack_now(wid, dtype, 0, 0, cin).data_ptr(), cout,
                    out.data_ptr(), None)
         assert torch.equal(out, x)
     # (b) tap counts
     ones = nhwc(torch.ones(n, cin, h, w, device=DEV, dtype=dtype))
     wone = torch.ones(cout, cin, 3, 3, device=DEV)
-    packed = unet_ops._pack_now(wone, dtype, 0, 0, cin)
+    packed = packcache._pack_now(wone, dtype, 0, 0, cin)
     out = nhwc(torch.empty(n, cout, h, w, device=DEV, dtype=dtype))
     _cabi.call("miseg_conv3x3_fwd", st, dt, ones.data_ptr(), cin, 0, None, 0, 0, n, h, w, packed.data_ptr(), cout, out.data_ptr(), None)
     r = torch.full((h,), 3.0); r[0] = r[-1] = 2.0
@@ -457,28 +457,36 @@ CHAIN_CASES = {
 }
 
 
-def _chain(dtype, case, fuse, monkeypatch):
+def _chain(dtype, case, fuse, monkeypatch, flat=False):
+    """``flat``: the parameters live in a ``FlatBuffers`` with open gradient slots; it is returned after the gradients."""
     from miseg_amd import unet_ops
+    from miseg_amd.flat import FlatBuffers
     monkeypatch.setattr(unet_ops, "_FUSE_BN_BWD", fuse)
     n, h, w, chain, up_at, cat_at = CHAIN_CASES[case]
     hin, win = (h // 2, w // 2) if up_at == 0 else (h, w)
     x = nhwc(T(synth.normal(f"chain/{case}/x", (n, chain[0], hin, win))).to(DEV).to(dtype)).requires_grad_(True)
-    params, acts = [], []
-    cur, cin = x, chain[0]
+    params, cin = [], chain[0]
+    for i, cout in enumerate(chain[1:]):
+        ctot = cin + (chain[1] if cat_at == i else 0)
+        wt = T(synth.normal(f"chain/{case}/w{i}", (cout, ctot, 3, 3), scale=(2.0 / (ctot * 9)) ** 0.5)).to(DEV)
+        bn = make_bn(cout, f"chain/{case}/bn{i}")
+        params += [torch.nn.Parameter(t) for t in (wt, bn["weight"].to(DEV), bn["bias"].to(DEV))]
+        cin = cout
+    fb = FlatBuffers(list(params)) if flat else None
+    if flat:
+        fb.zero_grad()
+    acts, cur = [], x
     for i, cout in enumerate(chain[1:]):
         x1 = acts[0] if cat_at == i else None
-        ctot = cin + (x1.shape[1] if x1 is not None else 0)
-        wt = T(synth.normal(f"chain/{case}/w{i}", (cout, ctot, 3, 3), scale=(2.0 / (ctot * 9)) ** 0.5)).to(DEV).requires_grad_(True)
         bn = make_bn(cout, f"chain/{case}/bn{i}")
-        g, b = bn["weight"].to(DEV).requires_grad_(True), bn["bias"].to(DEV).requires_grad_(True)
+        wt, g, b = params[3 * i:3 * i + 3]
         cur, _ = unet_ops.conv_bn_relu(cur, x1, wt, g, b, bn["running_mean"].to(DEV), bn["running_var"].to(DEV), bn["nbt"].to(DEV), True,
                                        1 if up_at == i else 0, 0, False)
-        params += [wt, g, b]
         acts.append(cur)
-        cin = cout
     cot = T(synth.normal(f"chain/{case}/cot", tuple(cur.shape))).to(DEV)
     (cur.float() * cot).sum().backward()
-    return [x.grad] + [p.grad for p in params]
+    grads = [x.grad] + [p.grad for p in params]
+    return (grads, fb) if flat else grads
 
 
 def _chain_reference(dtype, case):
@@ -547,6 +555,36 @@ def test_bn_backward_folded_into_the_convolutions(case, dtype, monkeypatch):
         rel_ref = float((a - r).norm() / (r.norm() + 1e-20))
         # (measured: bf16 <= 0.066 -- the gamma gradients, a cancelling sum --, half <= 0.015, fp32 <= 1.1e-3: a few masks at |y| ~ 1e-7)
         assert rel_ref <= (1e-1 if dtype == torch.bfloat16 else 3e-2 if half else 3e-3), (case, i, rel_ref)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_bn_backward_folded_with_weights_in_a_flat_buffer(dtype, monkeypatch):
+    """The folded backward with the parameters in a flat buffer: ``miseg_conv3x3_wgrad_bn`` runs on the weight-gradient side stream
+    through the fork the three-pass backward uses, into the flat slots.  After ``collect()`` every slot equals, bit for bit, the
+    gradient of the same chain run with plain tensors (same kernel, same operands), and the pass has joined the side stream."""
+    from miseg_amd import _cabi, unet_ops
+    case = "tiled_ragged"
+    plain = _chain(dtype, case, True, monkeypatch)
+    calls = []
+    real_call = _cabi.call
+
+    def spy(name, *a, **k):
+        calls.append((name, a))
+        return real_call(name, *a, **k)
+    monkeypatch.setattr("miseg_amd.unet_ops.call", spy)
+    unet_ops._wgrad_dirty.clear()
+    got, fb = _chain(dtype, case, True, monkeypatch, flat=True)
+    assert not unet_ops._wgrad_dirty
+    side = unet_ops.wgrad_stream(torch.device(DEV, torch.cuda.current_device())).cuda_stream
+    streams = [a[0] for nme, a in calls if nme == "miseg_conv3x3_wgrad_bn"]
+    assert streams == [side] * (len(CHAIN_CASES[case][3]) - 1) and side != torch.cuda.current_stream().cuda_stream, (streams, side)
+    fb.collect()
+    torch.cuda.synchronize()
+    assert torch.equal(got[0], plain[0])
+    for p, want in zip(fb.given, plain[1:]):
+        o = fb.offset_of(p)
+        assert torch.equal(fb.flat_grad[o:o + p.numel()].view_as(p), want), tuple(p.shape)
+        assert float(want.abs().max()) > 0
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
