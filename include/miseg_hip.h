@@ -731,6 +731,30 @@ int miseg_adabound_step(void* stream, float* param, const float* grad, float* ex
  * 16-byte aligned. */
 int miseg_ema_update(void* stream, float* teacher, const float* student, int64_t numel, const float* coef,
                      const float* guard, int64_t nguard);
+/* Interpolation consistency training (Trainer.name=ict; Verma et al. 2019, no counterpart in the reference: DESIGN.md section 27;
+ * csrc/ict.hip, library version 417).  A Mean Teacher whose student sees a convex mix of two unlabeled images and is held to the same
+ * mix of the teacher's two predictions.  Common to the three entry points: coef = device fp32[2] (c0, c1) and perm = device int32[N]
+ * (Nb for cat_mixed) -- both in the iteration's step block, so a replayed launch tape reads each step's values.  The mix is a gather:
+ * sample i's partner is perm[i].  A perm[i] outside [0, N) counts as i (no partner) and adds 1 to bad[0] (int32, may be NULL, never
+ * cleared here: the caller zeroes it); nothing is read out of range.  A mixed value is fma(c0, x, c1 * y): the product rounded, then
+ * one fused multiply-add, no reassociation across elements; (c0, c1) = (1, 0) gives x and (0, 1) gives y for finite operands.
+ * cat_mixed: out = [a | m], m_i = c0 * b_i + c1 * b_perm[i], contiguous [*,C,H,W] fp32; the Na rows of a (NULL with Na = 0) are copied
+ *              bit for bit.  16 bytes per lane where C*H*W is a multiple of 4 and the pointers are 16-byte aligned, else one float.
+ * softmax_mix_mse / softmax_mix_klcons: the layouts and arguments of miseg_softmax_mse (fp32 NHWC, a = student rows, b = teacher rows
+ *              of the same N, ws from miseg_loss_ws_bytes, upstream and ga may be NULL) with the target
+ *              q = c0 * softmax(b_i) + c1 * softmax(b_perm[i]) at the same pixel, detached, in place of softmax(flip(b)):
+ *              mse = mean((softmax(a) - q)^2) over N*C*H*W; klcons = mean_{n,h,w} sum_c -q_c*log((p_c+1e-16)/(q_c+1e-16)).
+ *              ga = upstream * d loss / d a; nothing flows to b.  Two launches, two-pass sums, no float atomics: deterministic.
+ * Refusals (MISEG_E_INVALID, nothing launched, nothing written): a class count outside 2-6, 8, 10, 16, an empty batch, a workspace
+ * below miseg_loss_ws_bytes, a NULL perm / coef / a (Na > 0) / b / loss / out / ws, cat_mixed in place. */
+int miseg_cat_mixed(void* stream, const float* a, int64_t Na, const float* b, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                    const int32_t* perm, const float* coef, float* out, int32_t* bad);
+int miseg_softmax_mix_mse(void* stream, const float* a, const float* b, const int32_t* perm, const float* coef, int64_t N, int64_t H,
+                          int64_t W, int64_t C, const float* upstream, float* loss, float* ga, int32_t* bad, void* ws,
+                          int64_t ws_bytes);
+int miseg_softmax_mix_klcons(void* stream, const float* a, const float* b, const int32_t* perm, const float* coef, int64_t N,
+                             int64_t H, int64_t W, int64_t C, const float* upstream, float* loss, float* ga, int32_t* bad, void* ws,
+                             int64_t ws_bytes);
 /* Overflow test of the half-precision modes (BASELINE configs[4]: torch.cuda.amp-style loss scaling; the reference itself trains in
  * fp32 and has no such step): count[0] = number of non-finite entries of grad[0..numel), as a float (0 = clean).  The caller appends
  * it to the guard flags of miseg_adam_step_guarded -- an overflowed gradient then moves neither parameters nor moments -- and the

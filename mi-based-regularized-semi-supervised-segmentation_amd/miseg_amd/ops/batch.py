@@ -1,4 +1,4 @@
-"""Batch assembly (csrc/batch.hip, affine.hip): per-sample flips, the affine warp, the network's input batches in one launch, and
+"""Batch assembly (csrc/batch.hip, affine.hip, ict.hip): per-sample flips, the affine warp, the network's input batches in one launch, and
 ``split_rows`` -- the split of the logits whose backward assembles the batch gradient in place, with the protocol
 (``_split_part_of``, ``_scaled_grad``) by which a loss kernel writes its part's rows itself."""
 from __future__ import annotations
@@ -8,8 +8,9 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from .. import _cabi, unet_ops
+from .. import _cabi, checks, unet_ops
 from .._rt import _DT, _need_gpu, _ptr, _stream, empty_nhwc, fill_zero
+from ..stepio import zero_counter
 from ._pkg import call
 
 
@@ -280,4 +281,21 @@ def cat_flipped(a: Tensor, b: Tensor, flips: Tensor) -> Tensor:
     assert flips.dtype == torch.int32 and flips.numel() >= nb
     out = torch.empty((na + nb,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
     call("miseg_cat_flipped", _stream(), _ptr(a), na, _ptr(b), nb, a.shape[1], a.shape[2], a.shape[3], _ptr(flips), _ptr(out))
+    return out
+
+
+def cat_mixed(a: Tensor, b: Tensor, perm: Tensor, coef: Tensor, check_perm: bool = True) -> Tensor:
+    """``torch.cat([a, coef[0] * b + coef[1] * b[perm]])`` along dim 0 in one launch: the ICT student's input batch (DESIGN.md section
+    27); the teacher reads ``b`` itself.  fp32 [N,C,H,W]; ``perm`` int32 [Nb] and ``coef`` fp32 [2] on the device (the iteration's step
+    block).  A ``perm[i]`` outside [0, Nb) mixes sample i with itself and is flagged; with ``check_perm`` the flag goes to
+    ``checks.require_zero``: raised here, or at the iteration's fetch inside a ``checks.deferred`` block."""
+    a, b, na, nb = _cat_operands(a, b, perm)
+    _need_gpu(coef)
+    assert a.dtype == torch.float32 and perm.dtype == torch.int32 and perm.numel() >= nb and perm.is_contiguous(), (a.dtype, perm.dtype, perm.shape)
+    assert coef.dtype == torch.float32 and coef.numel() >= 2 and coef.is_contiguous(), (coef.dtype, coef.shape)
+    out = torch.empty((na + nb,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
+    bad = zero_counter(a.device, (1,))
+    call("miseg_cat_mixed", _stream(), _ptr(a), na, _ptr(b), nb, a.shape[1], a.shape[2], a.shape[3], _ptr(perm), _ptr(coef), _ptr(out), _ptr(bad))
+    if check_perm:
+        checks.require_zero(bad, IndexError, f"cat_mixed: an entry of the permutation lies outside [0, {nb})")
     return out

@@ -1,4 +1,4 @@
-"""Pixel-wise losses on the logits (csrc/losses.hip, dice.hip): each is one fused kernel that also leaves the gradient of the
+"""Pixel-wise losses on the logits (csrc/losses.hip, dice.hip, ict.hip): each is one fused kernel that also leaves the gradient of the
 logits, which the backward only has to scale."""
 from __future__ import annotations
 
@@ -103,6 +103,48 @@ class _SoftmaxKLCons(_SoftmaxMSE):
 def softmax_kl_consistency(a: Tensor, b: Tensor, flips: Optional[Tensor] = None) -> Tensor:
     """KL_div()(softmax(a), softmax(flip(b)).detach()) -- the `UDARegCriterion.name: kl` consistency term, fused like softmax_mse."""
     return _SoftmaxKLCons.apply(a, b, flips)
+
+
+class _SoftmaxMixMSE(_ScaledGradLoss):
+    entry = "miseg_softmax_mix_mse"
+
+    @classmethod
+    def forward(cls, ctx, a: Tensor, b: Tensor, perm: Tensor, coef: Tensor, flag_box: list):
+        _need_gpu(a, b, perm, coef)
+        raw, a, b = a, logits_nhwc(a), logits_nhwc(b.detach())
+        n, c, h, w = a.shape
+        assert b.shape == a.shape and perm.dtype == torch.int32 and perm.numel() >= n and perm.is_contiguous(), (a.shape, b.shape, perm.dtype, perm.shape)
+        assert coef.dtype == torch.float32 and coef.numel() >= 2 and coef.is_contiguous(), (coef.dtype, coef.shape)
+        loss, ga = _outputs(ctx, raw, a)
+        bad = zero_counter(a.device, (1,))
+        ws = _ws(query("miseg_loss_ws_bytes", n, h, w), a.device)
+        call(cls.entry, _stream(), _ptr(a), _ptr(b), _ptr(perm), _ptr(coef), n, h, w, c, None, _ptr(loss), _ptr(ga), _ptr(bad), _ptr(ws), ws.numel())
+        flag_box.append(bad)      # the bad-index flag, handed over beside the graph as in _SoftmaxKL
+        return loss
+
+
+class _SoftmaxMixKLCons(_SoftmaxMixMSE):
+    entry = "miseg_softmax_mix_klcons"
+
+
+def _mix_loss(fn, name: str, a: Tensor, b: Tensor, perm: Tensor, coef: Tensor, check_perm: bool) -> Tensor:
+    flag_box: list = []
+    loss = fn.apply(a, b, perm, coef, flag_box)
+    if check_perm:
+        checks.require_zero(flag_box[0], IndexError, f"{name}: an entry of the permutation lies outside [0, {int(a.shape[0])})")
+    return loss
+
+
+def softmax_mix_mse(a: Tensor, b: Tensor, perm: Tensor, coef: Tensor, check_perm: bool = True) -> Tensor:
+    """mean((softmax(a) - q)**2) with q = coef[0] * softmax(b) + coef[1] * softmax(b[perm]), detached: the ICT consistency term
+    (DESIGN.md section 27), fused like ``softmax_mse``.  ``perm`` int32 [N] and ``coef`` fp32 [2] on the device.  A ``perm[i]`` outside
+    [0, N) counts as i and is flagged; with ``check_perm`` the flag goes to ``checks.require_zero`` as in ``softmax_kl``."""
+    return _mix_loss(_SoftmaxMixMSE, "softmax_mix_mse", a, b, perm, coef, check_perm)
+
+
+def softmax_mix_kl_consistency(a: Tensor, b: Tensor, perm: Tensor, coef: Tensor, check_perm: bool = True) -> Tensor:
+    """KL_div()(softmax(a), q) with the mixed target of ``softmax_mix_mse``: the ``ICTParameters.name: kl`` form."""
+    return _mix_loss(_SoftmaxMixKLCons, "softmax_mix_kl_consistency", a, b, perm, coef, check_perm)
 
 
 _LOSS_CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)     # MISEG_DISPATCH_C of csrc/losses.hip

@@ -21,6 +21,7 @@ import os
 import random
 from typing import List, Optional, Tuple, Union
 
+import numpy as np
 import torch
 from torch import Tensor, nn
 
@@ -339,11 +340,7 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         seed = random.randint(0, int(1e7))
         labeled_image, labeled_target, _, _, label_group = self._unzip_data(labeled_data, self._device)
         unlabeled_image, _unlabeled_target, *_ = self._unzip_data(unlabeled_data, self._device)
-        ub = len(unlabeled_image)
-        with FixRandomSeed(seed):
-            decisions = self._affine_transformer.decisions(ub)
-        # [flips of the UB unlabeled samples | UB zeros] (the tf branch is never re-flipped)
-        flip_masks = ops.flip_masks(list(decisions) + [[False, False]] * ub)
+        flip_masks = self._draw_words(seed, len(unlabeled_image))
         self._seed = seed
         io = self._io_for(labeled_image.device)
         tape = self._step_tape
@@ -352,6 +349,13 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         else:
             ticket = self._run_step(io, labeled_image, labeled_target, unlabeled_image, flip_masks)
         return ticket, None, label_group
+
+    def _draw_words(self, seed: int, ub: int) -> List[int]:
+        """The iteration's host draws under ``FixRandomSeed(seed)``, as the int32 words the step block stages in its flips slot:
+        [flips of the UB unlabeled samples | UB zeros] (the tf branch is never re-flipped)."""
+        with FixRandomSeed(seed):
+            decisions = self._affine_transformer.decisions(ub)
+        return ops.flip_masks(list(decisions) + [[False, False]] * ub)
 
     _io = None
     _step_tape = None
@@ -855,7 +859,11 @@ class MeanTeacherEpocher(TrainEpocher):
         self._optimizer.grad_scale = scale
         self._ema_row = len(rows)
         self._ema_updater.flats(self._teacher_model, self._optimizer.flat)     # the teacher's mirror of the student's flat buffer
-        return io.stage(flip_masks, list(rows) + [list(self._ema_updater.host_step()) + [0.0]], scale)
+        return io.stage(flip_masks, list(rows) + self._own_rows(), scale)
+
+    def _own_rows(self) -> List[List[float]]:
+        """The rows this epocher stages behind the optimiser's: the EMA's."""
+        return [list(self._ema_updater.host_step()) + [0.0]]
 
     def _tape_signature(self):
         m = self._ema_updater._mirror
@@ -868,7 +876,7 @@ class MeanTeacherEpocher(TrainEpocher):
         lb, ub = len(labeled_image), len(unlabeled_image)
         self._flips2 = flips2
         flips = flips2[:ub]
-        batch = self._assemble(labeled_image, unlabeled_image, flips, keep_unflipped=False)      # [labeled | flip(unlabeled)] (ref :176-181)
+        batch = self._student_batch(labeled_image, unlabeled_image, flips)
         with checks.deferred(self._pending.checks):
             with torch.no_grad():          # the teacher: train mode, its own batch statistics, no autograd (ref :187-188)
                 teacher_logits = self._teacher_model(unlabeled_image)
@@ -884,9 +892,88 @@ class MeanTeacherEpocher(TrainEpocher):
                                 getattr(self._optimizer, "last_guard", None))
         return inter, union
 
+    def _student_batch(self, labeled_image: Tensor, unlabeled_image: Tensor, flips: Tensor) -> Tensor:
+        """``[labeled | flip(unlabeled)]`` (ref :176-181)."""
+        return self._assemble(labeled_image, unlabeled_image, flips, keep_unflipped=False)
+
     def _consistency(self, student_tf_logits: Tensor, teacher_logits: Tensor, flips: Tensor):
         """``reg_criterion(softmax(student(flip(u))), softmax(flip(teacher(u))).detach())`` (ref :193-194)."""
         return consistency_loss(self._reg_criterion, student_tf_logits, teacher_logits, flips)
+
+
+def mix_consistency_loss(criterion: T_loss, student_logits: Tensor, teacher_logits: Tensor, perm: Tensor, coef: Tensor):
+    """``criterion(softmax(student(m)), q)`` with ``q = coef[0] * softmax(teacher(u)) + coef[1] * softmax(teacher(u))[perm]`` detached:
+    mixing, softmaxes and distance are one fused kernel for ``nn.MSELoss`` and the fused ``KL_div`` (``name: mse | kl``)."""
+    if isinstance(criterion, nn.MSELoss):
+        return LinearLoss.of(ops.softmax_mix_mse(student_logits, teacher_logits, perm, coef))
+    if isinstance(criterion, KL_div) and criterion.supports_fused():
+        return LinearLoss.of(ops.softmax_mix_kl_consistency(student_logits, teacher_logits, perm, coef))
+    # any other criterion object: on materialised operands
+    t = teacher_logits.detach().float().softmax(1)
+    return criterion(student_logits.softmax(1), coef[0] * t + coef[1] * t[perm.long()])
+
+
+class ICTEpocher(MeanTeacherEpocher):
+    """``ict``: interpolation consistency training (Verma et al. 2019; ``ICTParameters``) -- the Mean Teacher
+    iteration whose student sees a convex mix of two unlabeled images and is held to the same mix of the teacher's two predictions.
+    What differs from ``MeanTeacherEpocher``, by the numbers of its iteration:
+
+    1. the host draws, under ``FixRandomSeed(seed)`` and in this order, ``lam = float(numpy.random.beta(mix_alpha, mix_alpha))`` and
+       ``perm = numpy.random.permutation(UB)``; no flips are drawn or applied.  ``perm`` travels in the step block's flips slot and
+       ``(c0, c1) = (float32(lam), float32(1 - lam))`` in one more row behind the EMA's, so a replayed launch tape reads each
+       iteration's values;
+    3. the student's batch is ``[labeled | m]`` with ``m_i = c0 * u_i + c1 * u_perm[i]`` (one launch, ``ops.cat_mixed``);
+    4. the consistency target at a pixel is ``c0 * softmax(t_i) + c1 * softmax(t_perm[i])`` of the teacher's logits ``t`` on the
+       unmixed batch, mixed inside the loss kernel (``ops.softmax_mix_mse`` / ``ops.softmax_mix_kl_consistency``).
+
+    The teacher's forward, backward, the guarded optimiser, the EMA and the meters are ``MeanTeacherEpocher``'s.  An index of the
+    permutation outside the batch is one of the iteration's deferred checks (``IndexError`` at the fetch, the update skipped)."""
+
+    def __init__(self, model, teacher_model, optimizer, labeled_loader: T_loader, unlabeled_loader: T_loader, sup_criterion: T_loss,
+                 reg_criterion: T_loss, reg_weight: float, num_batches: int, cur_epoch=0, device="cpu", feature_position=None,
+                 feature_importance=None, ema_updater=None, mix_alpha: float = 1.0) -> None:
+        super().__init__(model, teacher_model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_criterion, reg_weight,
+                         num_batches, cur_epoch, device, feature_position, feature_importance, ema_updater)
+        if not float(mix_alpha) > 0.0:
+            raise ValueError(f"ICTEpocher: mix_alpha must be positive, got {mix_alpha}")
+        self._mix_alpha = float(mix_alpha)
+        self._mix = (1.0, 0.0)
+
+    @staticmethod
+    def draw_mix(seed: int, ub: int, mix_alpha: float) -> Tuple[float, List[int]]:
+        """``(lam, perm)`` of one iteration: under ``FixRandomSeed(seed)``, the Beta draw first, then the permutation."""
+        with FixRandomSeed(seed):
+            lam = float(np.random.beta(mix_alpha, mix_alpha))
+            perm = np.random.permutation(ub)
+        return lam, [int(p) for p in perm]
+
+    def _draw_words(self, seed: int, ub: int) -> List[int]:
+        lam, perm = self.draw_mix(seed, ub, self._mix_alpha)
+        self._mix = (lam, 1.0 - lam)           # the subtraction in double; the block stores both as float32
+        return perm
+
+    def _own_rows(self) -> List[List[float]]:
+        return super()._own_rows() + [[float(self._mix[0]), float(self._mix[1])]]
+
+    def _coef(self) -> Tensor:
+        return stepio.CURRENT.hyper(self._ema_row + 1)[:2]
+
+    def _tape_signature(self):
+        return super()._tape_signature() + (self._mix_alpha, self._criterion_signature(self._reg_criterion))
+
+    def _student_batch(self, labeled_image: Tensor, unlabeled_image: Tensor, perm: Tensor) -> Tensor:
+        """``[labeled | c0 * unlabeled + c1 * unlabeled[perm]]``: one launch where the kernel takes the operands."""
+        coef = self._coef()
+        if labeled_image.dtype == unlabeled_image.dtype == torch.float32 and labeled_image.dim() == 4 and \
+                labeled_image.shape[1:] == unlabeled_image.shape[1:] and labeled_image.is_cuda:
+            with checks.deferred(self._pending.checks):
+                return ops.cat_mixed(labeled_image, unlabeled_image, perm, coef)
+        wide = unlabeled_image.to(torch.promote_types(unlabeled_image.dtype, torch.float32))      # (16-bit images are mixed in fp32)
+        mixed = coef[0] * wide + coef[1] * wide[perm.long()]
+        return torch.cat([labeled_image, mixed.to(unlabeled_image.dtype)], dim=0)
+
+    def _consistency(self, student_logits: Tensor, teacher_logits: Tensor, perm: Tensor):
+        return mix_consistency_loss(self._reg_criterion, student_logits, teacher_logits, perm, self._coef())
 
 
 class MIDLTrainEpocher(UDATrainEpocher):

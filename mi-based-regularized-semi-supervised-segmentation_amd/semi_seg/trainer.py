@@ -2,7 +2,7 @@
 
 Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT, and ``midl`` and
 ``entmin``, the ``MIDLPaperParameters`` and ``EntropyMinParameters`` sections' trainers, ``vat``, virtual adversarial training on the
-wheel's ``VATLoss``, and ``contrast`` and ``contrastdecoder``, the
+wheel's ``VATLoss``, ``ict``, interpolation consistency training on the Mean Teacher, and ``contrast`` and ``contrastdecoder``, the
 encoder and decoder stages of the reference's contrastive pre-training), the keyword-only constructor, ``init()``,
 ``start_training()``, ``inference(checkpoint)``, ``set_feature_positions`` and the attribute names the checkpoint tree is
 keyed by (``_model``, ``_optimizer``, ``_scheduler``, ``_projector_wrappers``, ``_IIDSegWrapper``, ``_storage`` ...; the
@@ -260,7 +260,7 @@ class MeanTeacherTrainer(SemiTrainer):
         super()._init()
         from contrastyou.arch import UNet
         from deepclustering2.models import ema_updater
-        section = self._config["MeanTeacherParameters"]
+        section = self._teacher_section()
         self._reg_criterion, self._reg_weight = _consistency_section(section)
         self._teacher_model = UNet(**self._config["Arch"])
         for param in self._teacher_model.parameters():
@@ -270,6 +270,10 @@ class MeanTeacherTrainer(SemiTrainer):
         self._ema_updater = ema_updater(alpha=float(section["alpha"]), justify_alpha=True, weight_decay=float(section["weight_decay"]),
                                         update_bn=False)
 
+    def _teacher_section(self) -> dict:
+        """The section with the consistency term (``name``, ``weight``) and the EMA (``alpha``, ``weight_decay``)."""
+        return self._config["MeanTeacherParameters"]
+
     def _make_epocher(self):
         return E.MeanTeacherEpocher(self._model, self._teacher_model, self._optimizer, self._labeled_loader, self._unlabeled_loader,
                                     self._sup_criterion, reg_criterion=self._reg_criterion, reg_weight=self._reg_weight,
@@ -277,6 +281,42 @@ class MeanTeacherTrainer(SemiTrainer):
 
     def _inference_model(self):
         return self._teacher_model
+
+
+class ICTTrainer(MeanTeacherTrainer):
+    """``ict``: interpolation consistency training (Verma et al. 2019, the "MixUp" row of the semi-supervised comparisons) -- a Mean
+    Teacher whose student sees ``lam * u_i + (1 - lam) * u_perm[i]`` of two unlabeled images and is held, with ``ICTParameters.weight``
+    x consistency (``name``: mse | kl), to the same mix of the teacher's two predictions; ``lam ~ Beta(mix_alpha, mix_alpha)`` and the
+    permutation are drawn every iteration.  The section is optional: missing keys take the class's defaults.  Teacher, EMA
+    (``alpha``, ``weight_decay``), checkpoint tree and evaluation are ``meanteacher``'s.  Semantics: DESIGN.md section 27."""
+
+    DEFAULTS = dict(name="mse", weight=10.0, alpha=0.999, weight_decay=0.000001, mix_alpha=1.0)
+    NAME = "ict"
+
+    @classmethod
+    def parameters(cls, configuration) -> dict:
+        """``ICTParameters`` of a configuration over the defaults; unknown keys are an error, and so is ``mix_alpha <= 0``."""
+        section = dict((configuration or {}).get("ICTParameters") or {})
+        unknown = sorted(set(section) - set(cls.DEFAULTS))
+        if unknown:
+            raise KeyError(f"ICTParameters: unknown keys {unknown}; known: {sorted(cls.DEFAULTS)}")
+        merged = {**cls.DEFAULTS, **section}
+        if str(merged["name"]) not in _CONSISTENCY:
+            raise KeyError(f"ICTParameters.name={merged['name']}: one of {sorted(_CONSISTENCY)}")
+        if not float(merged["mix_alpha"]) > 0.0:
+            raise ValueError(f"ICTParameters.mix_alpha={merged['mix_alpha']}: the Beta distribution needs a positive parameter")
+        return dict(name=str(merged["name"]), weight=float(merged["weight"]), alpha=float(merged["alpha"]),
+                    weight_decay=float(merged["weight_decay"]), mix_alpha=float(merged["mix_alpha"]))
+
+    def _teacher_section(self) -> dict:
+        params = self.parameters(self._config)
+        self._mix_alpha = params.pop("mix_alpha")
+        return params
+
+    def _make_epocher(self):
+        return E.ICTEpocher(self._model, self._teacher_model, self._optimizer, self._labeled_loader, self._unlabeled_loader,
+                            self._sup_criterion, reg_criterion=self._reg_criterion, reg_weight=self._reg_weight,
+                            ema_updater=self._ema_updater, mix_alpha=self._mix_alpha, **self._epoch_args())
 
 
 class MIDLTrainer(UDATrainer):
@@ -496,4 +536,4 @@ class ContrastDecoderTrainer(ContrastTrainer):
 
 trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer, "meanteacher": MeanTeacherTrainer,
                 "midl": MIDLTrainer, "entmin": EntropyMinTrainer, "vat": VATTrainer, "contrast": ContrastTrainer,
-                "contrastdecoder": ContrastDecoderTrainer}
+                "contrastdecoder": ContrastDecoderTrainer, "ict": ICTTrainer}
