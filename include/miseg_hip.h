@@ -755,6 +755,32 @@ int miseg_softmax_mix_mse(void* stream, const float* a, const float* b, const in
 int miseg_softmax_mix_klcons(void* stream, const float* a, const float* b, const int32_t* perm, const float* coef, int64_t N,
                              int64_t H, int64_t W, int64_t C, const float* upstream, float* loss, float* ga, int32_t* bad, void* ws,
                              int64_t ws_bytes);
+/* Uncertainty-aware Mean Teacher (Trainer.name=uamt; Yu et al., MICCAI 2019, no counterpart in the reference: DESIGN.md section 28;
+ * csrc/uamt.hip, library version 418).  A Mean Teacher whose consistency term counts only where the teacher's predictive entropy,
+ * taken over `passes` noisy forward passes, lies below a threshold.  fp32 throughout; the pixel kernels read NHWC rows.
+ * noise_add:     out[p][i] = x[i] + min(max(sigma * z, -clip), clip) for p in [0, passes), i in [0, M), z = the standard normal
+ *                miseg_normal_fill defines for (seed64, offset = p * M + i); seed = device int32[2] (lo, hi), read by the kernel, so a
+ *                replayed launch tape sees each step's seed.  One multiply, a clamp, one add, nothing contracted; a function of
+ *                (seed, p, i) only, never of the launch geometry.  16 bytes per lane where M is a multiple of 4 and x and out are
+ *                16-byte aligned, else one float.  Refused: a NULL pointer, M <= 0, passes < 1, out overlapping x.
+ * softmax_accum: acc = first ? softmax(logits) : acc + softmax(logits) over the class axis, one fp32 add per element; the order of
+ *                the passes is the order of the calls.
+ * softmax_umse:  a = student logits, b = teacher logits (target, detached), acc = the sum softmax_accum left.  Per pixel
+ *                m = acc * inv_passes, unc = -sum_c m_c log(m_c + 1e-6), mask = unc < thr[0] (device fp32, strict), d = softmax(a) -
+ *                softmax(b); K = sum mask; loss = sum_pix mask sum_c d_c^2 / (C K + 1e-16);
+ *                ga = upstream * mask * 2 p_c (d_c - sum_k d_k p_k) / (C K + 1e-16), exactly +0.0 at a masked-out pixel; with K = 0
+ *                the loss is 0.0 and ga all zero.  kept = int64[1] K, stats = fp32[2] (K / (N H W), mean unc); upstream, ga, kept and
+ *                stats may each be NULL.  Three launches: per-block partials (two-pass sums, an exact integer count, no float
+ *                atomics) and the unscaled gradient, one finishing block, the gradient's scale -- formed in double, rounded once.
+ *                Deterministic.  ws: miseg_softmax_umse_ws_bytes(N, H, W) bytes, 8-byte aligned.
+ * Refusals of the two pixel entry points (MISEG_E_INVALID, nothing launched, nothing written): a class count outside 2-6, 8, 10, 16,
+ * an empty batch, a short workspace, a NULL logits / a / b / acc / thr / loss / ws. */
+int miseg_noise_add(void* stream, const float* x, int64_t M, int64_t passes, const int32_t* seed, float sigma, float clip, float* out);
+int miseg_softmax_accum(void* stream, const float* logits, int64_t N, int64_t H, int64_t W, int64_t C, int first, float* acc);
+int64_t miseg_softmax_umse_ws_bytes(int64_t N, int64_t H, int64_t W);
+int miseg_softmax_umse(void* stream, const float* a, const float* b, const float* acc, int64_t N, int64_t H, int64_t W, int64_t C,
+                       float inv_passes, const float* thr, const float* upstream, float* loss, float* ga, int64_t* kept, float* stats,
+                       void* ws, int64_t ws_bytes);
 /* Overflow test of the half-precision modes (BASELINE configs[4]: torch.cuda.amp-style loss scaling; the reference itself trains in
  * fp32 and has no such step): count[0] = number of non-finite entries of grad[0..numel), as a float (0 = clean).  The caller appends
  * it to the guard flags of miseg_adam_step_guarded -- an overflowed gradient then moves neither parameters nor moments -- and the

@@ -1,6 +1,7 @@
 // Virtual adversarial training (Trainer.name=vat): the per-sample L2 normalisation + perturbation and the counter-based normal
 // generator.  fp32 tensors, no storage type -- built once.  ref: whl:deepclustering2/utils/VAT.py (_l2_normalize, VATLoss.forward).
 #include "common.h"
+#include "philox.h"      // Philox4x32-10 + Box-Muller, shared with uamt.hip
 
 namespace miseg {
 
@@ -59,20 +60,6 @@ __global__ __launch_bounds__(256) void l2_apply_kernel(const float* __restrict__
     }
 }
 
-// ---- Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11)
-struct Philox4 { unsigned v[4]; };
-__device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-    constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const unsigned hi0 = __umulhi(M0, c0), lo0 = M0 * c0, hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-        const unsigned n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += W0; k1 += W1;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
-
 // one thread = one counter block = elements [4 b, 4 b + 4) of the stream, of which [offset, offset + numel) are written
 template <bool NORMAL>
 __global__ __launch_bounds__(256) void philox_fill_kernel(unsigned long long seed, unsigned long long offset, unsigned long long numel,
@@ -80,17 +67,9 @@ __global__ __launch_bounds__(256) void philox_fill_kernel(unsigned long long see
     const unsigned long long first = offset >> 2, nblk = ((offset + numel + 3) >> 2) - first;
     for (unsigned long long t = blockIdx.x * 256ull + threadIdx.x; t < nblk; t += (unsigned long long)gridDim.x * 256ull) {
         const unsigned long long b = first + t;
-        const Philox4 p = philox4x32_10((unsigned)b, (unsigned)(b >> 32), 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32));
+        const Philox4 p = philox_block(seed, b);
         float z[4];
-        if (NORMAL) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const float u1 = (float)((p.v[2 * q] >> 8) + 1u) * 0x1p-24f, u2 = (float)(p.v[2 * q + 1] >> 8) * 0x1p-24f;
-                const float rad = sqrtf(-2.f * logf(u1)), ang = 6.283185307179586f * u2;
-                z[2 * q] = rad * cosf(ang);
-                z[2 * q + 1] = rad * sinf(ang);
-            }
-        }
+        if (NORMAL) philox_normals(p, z);
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
             const unsigned long long j = 4ull * b + l;

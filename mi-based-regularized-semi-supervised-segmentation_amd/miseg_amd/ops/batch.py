@@ -1,4 +1,4 @@
-"""Batch assembly (csrc/batch.hip, affine.hip, ict.hip): per-sample flips, the affine warp, the network's input batches in one launch, and
+"""Batch assembly (csrc/batch.hip, affine.hip, ict.hip, uamt.hip): per-sample flips, the affine warp, the network's input batches in one launch, and
 ``split_rows`` -- the split of the logits whose backward assembles the batch gradient in place, with the protocol
 (``_split_part_of``, ``_scaled_grad``) by which a loss kernel writes its part's rows itself."""
 from __future__ import annotations
@@ -298,4 +298,18 @@ def cat_mixed(a: Tensor, b: Tensor, perm: Tensor, coef: Tensor, check_perm: bool
     call("miseg_cat_mixed", _stream(), _ptr(a), na, _ptr(b), nb, a.shape[1], a.shape[2], a.shape[3], _ptr(perm), _ptr(coef), _ptr(out), _ptr(bad))
     if check_perm:
         checks.require_zero(bad, IndexError, f"cat_mixed: an entry of the permutation lies outside [0, {nb})")
+    return out
+
+
+def noise_add(x: Tensor, seed: Tensor, passes: int, sigma: float, clip: float) -> Tensor:
+    """``stack([x + clamp(sigma * z[p], -clip, clip) for p in range(passes)])`` in one launch: the noisy copies the UA-MT teacher sees
+    (DESIGN.md section 28).  ``x`` fp32, contiguous; ``seed`` int32 [2] on the device (the low and high word of the 64-bit seed, in the
+    iteration's step block); element i of ``z[p]`` is ``normal_fill``'s standard normal for ``(seed, p * x.numel() + i)``.  ``sigma``
+    and ``clip`` are constants of the call (and of a recorded tape)."""
+    _need_gpu(x, seed)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0, (x.dtype, x.shape, x.stride())
+    assert seed.dtype == torch.int32 and seed.numel() >= 2 and seed.is_contiguous(), (seed.dtype, seed.shape)
+    assert int(passes) >= 1 and float(sigma) >= 0.0 and float(clip) >= 0.0, (passes, sigma, clip)
+    out = torch.empty((int(passes),) + tuple(x.shape), dtype=x.dtype, device=x.device)
+    call("miseg_noise_add", _stream(), _ptr(x), x.numel(), int(passes), _ptr(seed), float(sigma), float(clip), _ptr(out))
     return out

@@ -1,4 +1,4 @@
-"""Pixel-wise losses on the logits (csrc/losses.hip, dice.hip, ict.hip): each is one fused kernel that also leaves the gradient of the
+"""Pixel-wise losses on the logits (csrc/losses.hip, dice.hip, ict.hip, uamt.hip): each is one fused kernel that also leaves the gradient of the
 logits, which the backward only has to scale."""
 from __future__ import annotations
 
@@ -10,6 +10,7 @@ from torch import Tensor
 from .. import checks
 from .._cabi import query
 from .._rt import _need_gpu, _ptr, _stream, _ws, empty_nhwc, logits_nhwc
+from .. import stepio
 from ..stepio import scalar_out, zero_counter
 from ._pkg import call
 from .batch import _scaled_grad, _split_part_of       # the shared piece: a loss on a part of a split_rows writes that part's rows
@@ -145,6 +146,64 @@ def softmax_mix_mse(a: Tensor, b: Tensor, perm: Tensor, coef: Tensor, check_perm
 def softmax_mix_kl_consistency(a: Tensor, b: Tensor, perm: Tensor, coef: Tensor, check_perm: bool = True) -> Tensor:
     """KL_div()(softmax(a), q) with the mixed target of ``softmax_mix_mse``: the ``ICTParameters.name: kl`` form."""
     return _mix_loss(_SoftmaxMixKLCons, "softmax_mix_kl_consistency", a, b, perm, coef, check_perm)
+
+
+def softmax_accum(logits: Tensor, acc: Optional[Tensor] = None) -> Tensor:
+    """``softmax(logits, 1)`` into a new accumulator (``acc`` None) or added to ``acc`` in place: the sum of the UA-MT teacher's
+    predictions over its stochastic passes (DESIGN.md section 28).  The accumulator is fp32 NHWC (a channels_last [N,C,H,W] tensor);
+    the order of the additions is the order of the calls.  No autograd."""
+    _need_gpu(logits, acc)
+    logits = logits_nhwc(logits.detach())
+    n, c, h, w = logits.shape
+    first = acc is None
+    if first:
+        acc = empty_nhwc(n, c, h, w, torch.float32, logits.device)
+    assert acc.shape == logits.shape and acc.dtype == torch.float32 and acc.is_contiguous(memory_format=torch.channels_last), \
+        (acc.shape, acc.dtype, acc.stride())
+    call("miseg_softmax_accum", _stream(), _ptr(logits), n, h, w, c, int(first), _ptr(acc))
+    return acc
+
+
+def _kept_out(device) -> Tensor:
+    """int64[1] for the count of certain pixels: inside an iteration two adjacent counters of the step block (8-byte aligned; the
+    kernel writes both words), otherwise an ordinary allocation."""
+    io = stepio.CURRENT
+    if io is None or io.device != device:
+        return torch.empty(1, dtype=torch.int64, device=device)
+    lo = io.counter()
+    if lo.data_ptr() % 8:
+        lo = io.counter()
+    io.counter()
+    i = io.counter_index(lo)
+    return io.counters_base()[i:i + 2].view(torch.int64)
+
+
+class _SoftmaxUMSE(_ScaledGradLoss):
+    @staticmethod
+    def forward(ctx, a: Tensor, b: Tensor, acc: Tensor, thr: Tensor, passes: int, box: list):
+        _need_gpu(a, b, acc, thr)
+        raw, a, b, acc = a, logits_nhwc(a), logits_nhwc(b.detach()), logits_nhwc(acc.detach())
+        n, c, h, w = a.shape
+        assert b.shape == a.shape and acc.shape == a.shape, (a.shape, b.shape, acc.shape)
+        assert thr.dtype == torch.float32 and thr.numel() >= 1 and thr.is_contiguous(), (thr.dtype, thr.shape)
+        loss, ga = _outputs(ctx, raw, a)
+        kept, stats = _kept_out(a.device), scalar_out((2,), a.device)
+        ws = _ws(query("miseg_softmax_umse_ws_bytes", n, h, w), a.device)
+        call("miseg_softmax_umse", _stream(), _ptr(a), _ptr(b), _ptr(acc), n, h, w, c, 1.0 / int(passes), _ptr(thr), None, _ptr(loss),
+             _ptr(ga), _ptr(kept), _ptr(stats), _ptr(ws), ws.numel())
+        box.extend((kept, stats))      # handed over beside the graph, as the flag of _SoftmaxKL
+        return loss
+
+
+def softmax_umse(a: Tensor, b: Tensor, acc: Tensor, thr: Tensor, passes: int):
+    """The UA-MT consistency term, fused like ``softmax_mse``: with ``m = acc / passes``,
+    ``unc = -sum_c m_c log(m_c + 1e-6)`` and ``mask = unc < thr`` per pixel, ``sum(mask * (softmax(a) - softmax(b).detach())**2) /
+    (C * K + 1e-16)`` for ``K = sum(mask)``; 0 with a zero gradient where no pixel is certain.  ``acc``: the sum ``softmax_accum``
+    left; ``thr``: fp32 [1] on the device (the iteration's step block).  Returns ``(loss, kept, stats)``: ``kept`` int64 [1] = K,
+    ``stats`` fp32 [2] = (K / (N H W), mean unc).  The gradient flows to ``a`` only."""
+    box: list = []
+    loss = _SoftmaxUMSE.apply(a, b, acc, thr, int(passes), box)
+    return loss, box[0], box[1]
 
 
 _LOSS_CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)     # MISEG_DISPATCH_C of csrc/losses.hip

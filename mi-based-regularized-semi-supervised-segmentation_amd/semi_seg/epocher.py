@@ -17,6 +17,7 @@ regulariser, one backward, Adam (ref :137-188).  What changed underneath:
 """
 from __future__ import annotations
 
+import math
 import os
 import random
 from typing import List, Optional, Tuple, Union
@@ -879,7 +880,7 @@ class MeanTeacherEpocher(TrainEpocher):
         batch = self._student_batch(labeled_image, unlabeled_image, flips)
         with checks.deferred(self._pending.checks):
             with torch.no_grad():          # the teacher: train mode, its own batch statistics, no autograd (ref :187-188)
-                teacher_logits = self._teacher_model(unlabeled_image)
+                teacher_logits = self._teacher_forward(unlabeled_image)
             predict_logits = self._forward(batch, ub)
         label_logits, unlabel_tf_logits = ops.split_rows(predict_logits, [lb, ub])
         labels = labeled_target.squeeze(1)
@@ -891,6 +892,10 @@ class MeanTeacherEpocher(TrainEpocher):
         self._ema_updater.apply(self._teacher_model, self._optimizer.flat, stepio.CURRENT.hyper(self._ema_row)[:3],
                                 getattr(self._optimizer, "last_guard", None))
         return inter, union
+
+    def _teacher_forward(self, unlabeled_image: Tensor) -> Tensor:
+        """The teacher's logits the consistency term is held to: one tracked training forward on the unlabeled batch."""
+        return self._teacher_model(unlabeled_image)
 
     def _student_batch(self, labeled_image: Tensor, unlabeled_image: Tensor, flips: Tensor) -> Tensor:
         """``[labeled | flip(unlabeled)]`` (ref :176-181)."""
@@ -974,6 +979,111 @@ class ICTEpocher(MeanTeacherEpocher):
 
     def _consistency(self, student_logits: Tensor, teacher_logits: Tensor, perm: Tensor):
         return mix_consistency_loss(self._reg_criterion, student_logits, teacher_logits, perm, self._coef())
+
+
+def uamt_threshold(k: int, k_total: int, start: float, end: float, num_classes: int) -> float:
+    """UA-MT's uncertainty threshold at iteration ``k`` of ``k_total``, in double: the fraction ``start + (end - start) *
+    exp(-5 (1 - min(k / k_total, 1))^2)`` of the largest entropy ``ln(num_classes)``."""
+    r = min(float(k) / float(max(int(k_total), 1)), 1.0)
+    return (float(start) + (float(end) - float(start)) * math.exp(-5.0 * (1.0 - r) ** 2)) * math.log(float(num_classes))
+
+
+class UAMTEpocher(MeanTeacherEpocher):
+    """``uamt``: the uncertainty-aware Mean Teacher (Yu et al., MICCAI 2019; ``UAMTParameters``) -- the Mean
+    Teacher iteration whose consistency term counts only where the teacher is certain.  What differs from ``MeanTeacherEpocher``, by
+    the numbers of its iteration:
+
+    1. no flips are drawn or applied; the host computes the threshold ``thr = uamt_threshold(k, k_total, ...)`` of iteration
+       ``k = cur_epoch * num_batches + i``.  The flips slot of the step block holds UB zeros (the student's batch is the plain
+       concatenation) and then the two 32-bit halves of the iteration's seed; ``thr`` is word 0 of one more row behind the EMA's;
+    2. one launch (``ops.noise_add``) writes the ``1 + passes`` noisy copies ``x[p] = u + clamp(noise_sigma * z[p], +-noise_clip)``,
+       the generator seeded from the device words.  The teacher's tracked forward sees ``x[0]``; ``passes`` more forwards under
+       ``unet_ops.bn_untracked()`` see ``x[1..]`` and their softmaxes are summed (``ops.softmax_accum``): these move no BatchNorm
+       buffer, so the evaluated teacher does not depend on ``passes``;
+    3. the student's batch is ``[labeled | u]``, the unlabeled images clean;
+    4. the consistency term is ``ops.softmax_umse``: the squared distance of the two softmaxes over the pixels whose predictive
+       entropy lies below ``thr``, normalised by their count.
+
+    Backward, the guarded optimiser, the EMA and the meters are ``MeanTeacherEpocher``'s; ``uncertainty`` (mean predictive entropy),
+    ``certain`` (share of the pixels below the threshold) and ``threshold`` come on top.  Images must be fp32 4-D tensors: there is no
+    torch composition to fall back on, it would freeze the seed under the launch tape."""
+
+    METERS = ("uncertainty", "certain", "threshold")
+
+    def __init__(self, model, teacher_model, optimizer, labeled_loader: T_loader, unlabeled_loader: T_loader, sup_criterion: T_loss,
+                 reg_criterion: T_loss, reg_weight: float, num_batches: int, cur_epoch=0, device="cpu", feature_position=None,
+                 feature_importance=None, ema_updater=None, passes: int = 8, noise_sigma: float = 0.1, noise_clip: float = 0.2,
+                 threshold_start: float = 0.75, threshold_end: float = 1.0, k_total: Optional[int] = None) -> None:
+        super().__init__(model, teacher_model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_criterion, reg_weight,
+                         num_batches, cur_epoch, device, feature_position, feature_importance, ema_updater)
+        if not isinstance(reg_criterion, nn.MSELoss):
+            raise KeyError("UAMTEpocher: the masked consistency term is the squared distance (name: mse)")
+        if not 1 <= int(passes) <= 32:
+            raise ValueError(f"UAMTEpocher: passes must lie in 1..32, got {passes}")
+        if float(noise_sigma) < 0.0 or float(noise_clip) < 0.0:
+            raise ValueError(f"UAMTEpocher: noise_sigma and noise_clip must not be negative, got {noise_sigma}, {noise_clip}")
+        if not 0.0 <= float(threshold_start) <= float(threshold_end):
+            raise ValueError(f"UAMTEpocher: 0 <= threshold_start <= threshold_end, got {threshold_start}, {threshold_end}")
+        self._passes, self._noise_sigma, self._noise_clip = int(passes), float(noise_sigma), float(noise_clip)
+        self._threshold = (float(threshold_start), float(threshold_end))
+        self._k_total = int(k_total) if k_total is not None else int(num_batches)
+        self._TRAIN_FORWARDS = 2 + self._passes      # the step block's BatchNorm accumulator room (stepio.block_bytes)
+        self._iteration = 0
+        self._thr = 0.0
+        self._thr_sent: List[float] = []             # thresholds of the iterations whose read-back is still under way
+        self._acc = None
+
+    def threshold_at(self, i: int) -> float:
+        """The threshold of iteration ``i`` (from 0) of this epoch: a function of ``cur_epoch`` and ``i`` only."""
+        return uamt_threshold(self._cur_epoch * self._num_batches + i, self._k_total, *self._threshold, self.num_classes)
+
+    def _draw_words(self, seed: int, ub: int) -> List[int]:
+        self._thr = self.threshold_at(self._iteration)
+        self._iteration += 1
+        self._thr_sent.append(self._thr)
+        lo, hi = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+        return [0] * ub + [w - (1 << 32) if w >= (1 << 31) else w for w in (lo, hi)]
+
+    def _own_rows(self) -> List[List[float]]:
+        return super()._own_rows() + [[float(self._thr)]]
+
+    def _thr_word(self) -> Tensor:
+        return stepio.CURRENT.hyper(self._ema_row + 1)[:1]
+
+    def _tape_signature(self):
+        return super()._tape_signature() + (self._passes, self._noise_sigma, self._noise_clip) + self._threshold
+
+    def _student_batch(self, labeled_image: Tensor, unlabeled_image: Tensor, flips: Tensor) -> Tensor:
+        """``[labeled | unlabeled]``: the flips are zeros, ``_assemble``'s one launch is the plain concatenation."""
+        for image in (labeled_image, unlabeled_image):
+            if not (torch.is_tensor(image) and image.dtype == torch.float32 and image.dim() == 4 and image.is_cuda):
+                raise TypeError(f"Trainer.name=uamt takes fp32 [N,C,H,W] image batches on the GPU, got "
+                                f"{getattr(image, 'dtype', type(image))} {tuple(getattr(image, 'shape', ()))}")
+        if labeled_image.shape[1:] != unlabeled_image.shape[1:]:
+            raise TypeError(f"Trainer.name=uamt: labeled {tuple(labeled_image.shape)} and unlabeled {tuple(unlabeled_image.shape)} images differ")
+        return self._assemble(labeled_image, unlabeled_image, flips, keep_unflipped=False)
+
+    def _teacher_forward(self, unlabeled_image: Tensor) -> Tensor:
+        ub = len(unlabeled_image)
+        noisy = ops.noise_add(unlabeled_image.contiguous(), self._flips2[ub:ub + 2], 1 + self._passes, self._noise_sigma, self._noise_clip)
+        teacher_logits = self._teacher_model(noisy[0])           # tracked, as MeanTeacherEpocher's
+        acc = None
+        with unet_ops.bn_untracked():
+            for p in range(1, 1 + self._passes):
+                acc = ops.softmax_accum(self._teacher_model(noisy[p]), acc)
+        self._acc = acc
+        return teacher_logits
+
+    def _consistency(self, student_logits: Tensor, teacher_logits: Tensor, flips: Tensor):
+        loss, _kept, stats = ops.softmax_umse(student_logits, teacher_logits, self._acc, self._thr_word(), self._passes)
+        self._acc = None
+        self._pending.put("certain", stats[0])
+        self._pending.put("uncertainty", stats[1])
+        return LinearLoss.of(loss)
+
+    def _record(self, host: dict, inter: Tensor, union: Tensor, label_group) -> None:
+        super()._record(host, inter, union, label_group)
+        self.meters["threshold"].add(self._thr_sent.pop(0))       # records arrive in the order of the iterations
 
 
 class MIDLTrainEpocher(UDATrainEpocher):

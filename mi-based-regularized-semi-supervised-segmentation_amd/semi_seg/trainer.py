@@ -2,7 +2,7 @@
 
 Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT, and ``midl`` and
 ``entmin``, the ``MIDLPaperParameters`` and ``EntropyMinParameters`` sections' trainers, ``vat``, virtual adversarial training on the
-wheel's ``VATLoss``, ``ict``, interpolation consistency training on the Mean Teacher, and ``contrast`` and ``contrastdecoder``, the
+wheel's ``VATLoss``, ``ict``, interpolation consistency training on the Mean Teacher, ``uamt``, the uncertainty-aware Mean Teacher, and ``contrast`` and ``contrastdecoder``, the
 encoder and decoder stages of the reference's contrastive pre-training), the keyword-only constructor, ``init()``,
 ``start_training()``, ``inference(checkpoint)``, ``set_feature_positions`` and the attribute names the checkpoint tree is
 keyed by (``_model``, ``_optimizer``, ``_scheduler``, ``_projector_wrappers``, ``_IIDSegWrapper``, ``_storage`` ...; the
@@ -319,6 +319,54 @@ class ICTTrainer(MeanTeacherTrainer):
                             ema_updater=self._ema_updater, mix_alpha=self._mix_alpha, **self._epoch_args())
 
 
+class UAMTTrainer(MeanTeacherTrainer):
+    """``uamt``: the uncertainty-aware Mean Teacher (Yu et al., MICCAI 2019) -- a Mean Teacher whose teacher sees the unlabeled batch
+    under clipped Gaussian noise (``noise_sigma``, ``noise_clip``), runs ``passes`` more stochastic forwards for a per-pixel predictive
+    entropy, and whose ``UAMTParameters.weight`` x squared-distance consistency counts only where that entropy lies below a threshold
+    ramping from ``threshold_start`` to ``threshold_end`` (fractions of ``ln C``) over the run.  The section is optional: missing keys
+    take the class's defaults.  Teacher, EMA (``alpha``, ``weight_decay``), checkpoint tree and evaluation are ``meanteacher``'s.
+    Semantics: DESIGN.md section 28."""
+
+    DEFAULTS = dict(name="mse", weight=0.1, alpha=0.99, weight_decay=0.000001, passes=8, noise_sigma=0.1, noise_clip=0.2,
+                    threshold_start=0.75, threshold_end=1.0)
+    NAME = "uamt"
+    SINGLE_PROCESS = "the count of certain pixels would have to be all-reduced before the gradient is scaled"
+
+    @classmethod
+    def parameters(cls, configuration) -> dict:
+        """``UAMTParameters`` of a configuration over the defaults.  ``KeyError``: an unknown key, a ``name`` other than mse (UA-MT
+        defines no KL form); ``ValueError``: ``passes`` outside 1..32, a negative ``noise_sigma`` / ``noise_clip`` / threshold,
+        ``threshold_start > threshold_end``."""
+        section = dict((configuration or {}).get("UAMTParameters") or {})
+        unknown = sorted(set(section) - set(cls.DEFAULTS))
+        if unknown:
+            raise KeyError(f"UAMTParameters: unknown keys {unknown}; known: {sorted(cls.DEFAULTS)}")
+        merged = {**cls.DEFAULTS, **section}
+        if str(merged["name"]) != "mse":
+            raise KeyError(f"UAMTParameters.name={merged['name']}: mse (the masked term has no KL form)")
+        out = dict(name="mse", weight=float(merged["weight"]), alpha=float(merged["alpha"]), weight_decay=float(merged["weight_decay"]),
+                   passes=int(merged["passes"]), noise_sigma=float(merged["noise_sigma"]), noise_clip=float(merged["noise_clip"]),
+                   threshold_start=float(merged["threshold_start"]), threshold_end=float(merged["threshold_end"]))
+        if float(merged["passes"]) != out["passes"] or not 1 <= out["passes"] <= 32:
+            raise ValueError(f"UAMTParameters.passes={merged['passes']}: a whole number in 1..32")
+        if out["noise_sigma"] < 0.0 or out["noise_clip"] < 0.0:
+            raise ValueError(f"UAMTParameters: noise_sigma={out['noise_sigma']} and noise_clip={out['noise_clip']} must not be negative")
+        if out["threshold_start"] < 0.0 or out["threshold_end"] < 0.0 or out["threshold_start"] > out["threshold_end"]:
+            raise ValueError(f"UAMTParameters: 0 <= threshold_start={out['threshold_start']} <= threshold_end={out['threshold_end']}")
+        return out
+
+    def _teacher_section(self) -> dict:
+        params = self.parameters(self._config)
+        self._uamt = {k: params.pop(k) for k in ("passes", "noise_sigma", "noise_clip", "threshold_start", "threshold_end")}
+        return params
+
+    def _make_epocher(self):
+        return E.UAMTEpocher(self._model, self._teacher_model, self._optimizer, self._labeled_loader, self._unlabeled_loader,
+                             self._sup_criterion, reg_criterion=self._reg_criterion, reg_weight=self._reg_weight,
+                             ema_updater=self._ema_updater, k_total=self._max_epoch * self._num_batches, **self._uamt,
+                             **self._epoch_args())
+
+
 class MIDLTrainer(UDATrainer):
     """``midl``: ``UDARegCriterion.weight`` x consistency + ``MIDLPaperParameters.iic_weight`` x the local mutual information of the
     network's output (``IIDSegmentationSmallPathLoss(padding, patch_size)`` on softmax(flip(f(x))) and softmax(f(flip(x)))); the
@@ -536,4 +584,4 @@ class ContrastDecoderTrainer(ContrastTrainer):
 
 trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer, "meanteacher": MeanTeacherTrainer,
                 "midl": MIDLTrainer, "entmin": EntropyMinTrainer, "vat": VATTrainer, "contrast": ContrastTrainer,
-                "contrastdecoder": ContrastDecoderTrainer, "ict": ICTTrainer}
+                "contrastdecoder": ContrastDecoderTrainer, "ict": ICTTrainer, "uamt": UAMTTrainer}
