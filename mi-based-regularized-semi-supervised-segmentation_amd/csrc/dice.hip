@@ -11,7 +11,7 @@
 //   3. dice_grad_kernel       (only with glogits) softmax again, g_c = a [label == c] + b p_c^(pow-1) (+ the KL term at the label's
 //                             class), dz_c = p_c (g_c - <g, p>).
 // A label outside [0, C) sets *bad_label; that pixel adds to none of the sums and its gradient row is written as zeros.
-#include "common.h"
+#include "pixel_loss.h"
 
 namespace miseg {
 namespace dice {
@@ -22,14 +22,6 @@ constexpr int kMaxBps = 128;    // blocks per sample: a sample with more than kM
 constexpr int kFT = 1024;       // threads of the finish block
 constexpr int kTPE = 16;        // ... of which this many adjacent lanes sum one (sample, class)
 constexpr int kEPR = kFT / kTPE;
-
-__device__ __forceinline__ void softmax_c(const float* __restrict__ z, int C, float* p) {
-    float mx = -3.4e38f;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); s += p[c]; }
-    for (int c = 0; c < C; ++c) p[c] = p[c] / s;
-}
 
 __device__ __forceinline__ int wave_sum_int(int v) {
 #pragma unroll
@@ -216,8 +208,6 @@ __global__ __launch_bounds__(kDT) void dice_grad_kernel(const float* __restrict_
     }
 }
 
-static bool class_count_has_kernel(int64_t C) { return (C >= 2 && C <= 6) || C == 8 || C == 10 || C == 16; }
-
 }  // namespace dice
 }  // namespace miseg
 
@@ -229,23 +219,13 @@ extern "C" int64_t miseg_softmax_dice_ws_bytes(int64_t N, int64_t H, int64_t W, 
     return layout(N, C, blocks_per_sample(H * W)).end * 4;
 }
 
-#define MISEG_DICE_DISPATCH(C, POW, KL, MACRO)                                 \
-    switch (C) {                                                               \
-        case 2: MACRO(2, POW, KL); break;                                      \
-        case 3: MACRO(3, POW, KL); break;                                      \
-        case 4: MACRO(4, POW, KL); break;                                      \
-        case 5: MACRO(5, POW, KL); break;                                      \
-        case 6: MACRO(6, POW, KL); break;                                      \
-        case 8: MACRO(8, POW, KL); break;                                      \
-        case 10: MACRO(10, POW, KL); break;                                    \
-        default: MACRO(16, POW, KL); break;                                    \
-    }
+// MACRO(C, POW, KL) at the call's class count and power, with or without the KL term
 #define MISEG_DICE_VARIANT(C, MACRO)                                                  \
     do {                                                                              \
         if (pow == 1) {                                                               \
-            if (with_kl) { MISEG_DICE_DISPATCH(C, 1, true, MACRO) } else { MISEG_DICE_DISPATCH(C, 1, false, MACRO) } \
+            if (with_kl) { MISEG_DISPATCH_C(C, MACRO, 1, true) } else { MISEG_DISPATCH_C(C, MACRO, 1, false) } \
         } else {                                                                      \
-            if (with_kl) { MISEG_DICE_DISPATCH(C, 2, true, MACRO) } else { MISEG_DICE_DISPATCH(C, 2, false, MACRO) } \
+            if (with_kl) { MISEG_DISPATCH_C(C, MACRO, 2, true) } else { MISEG_DISPATCH_C(C, MACRO, 2, false) } \
         }                                                                             \
     } while (0)
 

@@ -8,29 +8,21 @@
 //
 // All three are HBM-bound: cat_mixed moves 16 bytes per lane where a sample is a whole number of 16-byte vectors; the losses take one
 // pixel per thread with the channel vectors in registers (one 16-byte load per row where C is a multiple of 4) and sum in two
-// deterministic passes (per-block partial -> one finishing block), as the pixel losses of losses.hip do.  Like dice.hip this unit
-// carries its own copy of the small helpers of that file (softmax_c, the finishing sum, the class-count dispatch): losses.hip stays
-// byte for byte what it was, and with it the bits of every loss the other trainers compute.
+// deterministic passes (per-block partial -> one finishing block), as the pixel losses of losses.hip do, with the helpers those use
+// (pixel_loss.h: softmax_c, the row loads, the class-count dispatch; the finishing sum is the kernel of losses.hip).
 //
 // Rounding: a mixed value is fma(c0, x, c1 * y) -- the product c1 * y rounded, then one fused multiply-add -- pinned by intrinsics
 // whatever -ffp-contract says.  With (c0, c1) = (1, 0) it is x and with (0, 1) it is y, exactly (finite operands; a zero keeps its
 // value, not always its sign).
-#include "common.h"
+#include "pixel_loss.h"
 
 namespace miseg {
 namespace ict {
 
 constexpr int kT = 256;
+static_assert(kT == kPixelThreads, "pixel_blocks() counts blocks of kT pixels");
 
 __device__ __forceinline__ float mix(float c0, float x, float c1, float y) { return __fmaf_rn(c0, x, __fmul_rn(c1, y)); }
-
-__device__ __forceinline__ void softmax_c(const float* __restrict__ z, int C, float* p) {
-    float mx = -3.4e38f;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); s += p[c]; }
-    for (int c = 0; c < C; ++c) p[c] = p[c] / s;
-}
 
 // sample i's partner, or i itself where perm[i] is no sample of the batch (`first`: one thread per sample reports it)
 __device__ __forceinline__ int64_t partner(const int32_t* __restrict__ perm, int64_t i, int64_t N, bool first, int32_t* __restrict__ bad) {
@@ -66,31 +58,6 @@ __global__ __launch_bounds__(kT) void cat_mixed_kernel(const float* __restrict__
 }
 
 // ---- the two consistency losses -----------------------------------------------------------------------------------------------
-template <int C, bool V4>
-__device__ __forceinline__ void load_row(const float* __restrict__ p, float* z) {
-    if (V4) {
-#pragma unroll
-        for (int c = 0; c < C; c += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(p + c);
-            z[c] = v.x; z[c + 1] = v.y; z[c + 2] = v.z; z[c + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) z[c] = p[c];
-    }
-}
-
-template <int C, bool V4>
-__device__ __forceinline__ void store_row(float* __restrict__ p, const float* z) {
-    if (V4) {
-#pragma unroll
-        for (int c = 0; c < C; c += 4) *reinterpret_cast<float4*>(p + c) = make_float4(z[c], z[c + 1], z[c + 2], z[c + 3]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) p[c] = z[c];
-    }
-}
-
 // KL: the klcons form, else the MSE.  d/da_c = p_c (g_c - <g, p>) through the softmax Jacobian, with g = 2 (p - q) / (npix C) (MSE;
 // the factor sits in `up`) or g_c = -q_c / (p_c + eps) / npix (KL).  Nothing flows to b.
 template <int C, bool V4, bool KL>
@@ -138,33 +105,6 @@ __global__ __launch_bounds__(kT) void mix_loss_kernel(const float* __restrict__ 
     if (threadIdx.x == 0) partials[blockIdx.x] = part;
 }
 
-// the partials in a fixed order (independent loads first), as the finishing block of losses.hip
-__global__ __launch_bounds__(256) void finish_sum_kernel(const float* __restrict__ partials, int n, float scale, float* __restrict__ out) {
-    __shared__ float red[17];
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { const int i = threadIdx.x + 256 * j; v[j] = i < n ? partials[i] : 0.f; }
-    float s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    for (int i = threadIdx.x + 2048; i < n; i += 256) s += partials[i];
-    s = block_sum(s, red);
-    if (threadIdx.x == 0) out[0] = s * scale;
-}
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static bool class_count_has_kernel(int64_t C) { return (C >= 2 && C <= 6) || C == 8 || C == 10 || C == 16; }
-
-#define MISEG_ICT_DISPATCH_C(C, MACRO)       \
-    switch (C) {                             \
-        case 2: MACRO(2, false); break;      \
-        case 3: MACRO(3, false); break;      \
-        case 4: if (v4) MACRO(4, true); else MACRO(4, false); break;   \
-        case 5: MACRO(5, false); break;      \
-        case 6: MACRO(6, false); break;      \
-        case 8: if (v4) MACRO(8, true); else MACRO(8, false); break;   \
-        case 10: MACRO(10, false); break;    \
-        default: if (v4) MACRO(16, true); else MACRO(16, false); break; \
-    }
-
 template <bool KL>
 static int mix_loss(const char* who, void* stream, const float* a, const float* b, const int32_t* perm, const float* coef, int64_t N, int64_t H,
                     int64_t W, int64_t C, const float* upstream, float* loss, float* ga, int32_t* bad, void* ws, int64_t ws_bytes) {
@@ -174,16 +114,14 @@ static int mix_loss(const char* who, void* stream, const float* a, const float* 
     const int64_t need = miseg_loss_ws_bytes(N, H, W);
     if (ws_bytes < need) return fail(MISEG_E_INVALID, "%s: workspace of %ld bytes, %ld needed", who, (long)ws_bytes, (long)need);
     const int64_t npix = N * H * W;
-    const int nb = (int)(need / 4);
+    const int nb = pixel_blocks(npix);
     const bool v4 = C % 4 == 0 && aligned16(a) && aligned16(b) && (!ga || aligned16(ga));
     hipStream_t st = as_stream(stream);
 #define L(CC, VV) hipLaunchKernelGGL((mix_loss_kernel<CC, VV, KL>), dim3(nb), dim3(kT), 0, st, a, b, perm, coef, N, H * W, npix, upstream, (float*)ws, ga, bad)
-    MISEG_ICT_DISPATCH_C(C, L)
+    MISEG_DISPATCH_C_V4(C, v4, L)
 #undef L
     MISEG_LAUNCH_CHECK("mix_loss_kernel");
-    hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nb, 1.0f / (KL ? (float)npix : (float)npix * (float)C), loss);
-    MISEG_LAUNCH_CHECK("finish_sum_kernel");
-    return MISEG_OK;
+    return launch_finish_sum(st, (const float*)ws, nb, 1.0f / (KL ? (float)npix : (float)npix * (float)C), loss);
 }
 
 }  // namespace ict
@@ -198,7 +136,7 @@ extern "C" int miseg_cat_mixed(void* stream, const float* a, int64_t Na, const f
     MISEG_REQUIRE(Na >= 0 && Nb > 0 && Nb < (1LL << 31) && C > 0 && H > 0 && W > 0, "cat_mixed: empty batch / bad shape");
     MISEG_REQUIRE(out != b && out != a, "cat_mixed: in-place not supported");
     const int64_t per = C * H * W;
-    const bool vec = per % 4 == 0 && ict::aligned16(out) && ict::aligned16(b) && (Na == 0 || ict::aligned16(a));
+    const bool vec = per % 4 == 0 && aligned16(out) && aligned16(b) && (Na == 0 || aligned16(a));
     const int64_t units = (Na + Nb) * (vec ? per / 4 : per);
     const dim3 grid((unsigned)std::min<int64_t>(cdiv(units, ict::kT), 2048));
     if (vec) hipLaunchKernelGGL(ict::cat_mixed_kernel<true>, grid, dim3(ict::kT), 0, as_stream(stream), a, b, out, Na, Nb, per / 4, perm, coef, bad);

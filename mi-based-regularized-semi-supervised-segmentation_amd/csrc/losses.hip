@@ -3,20 +3,12 @@
 // deterministic sums (per-block partial -> single-block finish).
 #include <hip/hip_fp16.h>
 
-#include "common.h"
+#include "pixel_loss.h"
 
 namespace miseg {
 
 constexpr int kLT = 256;
-constexpr int kMaxC = 32;
-
-__device__ __forceinline__ void softmax_c(const float* __restrict__ z, int C, float* p) {
-    float mx = -3.4e38f;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); s += p[c]; }
-    for (int c = 0; c < C; ++c) p[c] = p[c] / s;
-}
+static_assert(kLT == kPixelThreads, "pixel_blocks() counts blocks of kLT pixels");
 
 // The gradient row of a pixel whose label is out of range.  Out of line on purpose: with these stores inside softmax_kl_kernel's
 // branch the compiler laid the loop out differently and contracted two additions of the VALID path into FMAs -- the gradient moved in
@@ -177,6 +169,12 @@ __global__ __launch_bounds__(256) void finish_sum_kernel(const float* __restrict
     if (threadIdx.x == 0) out[0] = s * scale;
 }
 
+int launch_finish_sum(hipStream_t st, const float* partials, int n, float scale, float* out) {
+    hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, st, partials, n, scale, out);
+    MISEG_LAUNCH_CHECK("finish_sum_kernel");
+    return MISEG_OK;
+}
+
 template <typename E>
 __global__ void flip_kernel(const E* __restrict__ in, E* __restrict__ out, int N, int C, int H, int W, int64_t is0, int64_t is1,
                             int64_t is2, int64_t is3, int64_t os0, int64_t os1, int64_t os2, int64_t os3,
@@ -221,8 +219,6 @@ __global__ __launch_bounds__(256) void argmax_dice_kernel(const float* __restric
         atomicAdd(&uni[n * C + threadIdx.x], (unsigned long long)su[threadIdx.x]);
     }
 }
-
-static int loss_blocks(int64_t npix) { return (int)std::min<int64_t>(cdiv(npix, kLT), 2048); }
 
 // one thread per (outer, inner) position, channel stride = inner: coalesced along inner
 __global__ __launch_bounds__(256) void simplex_violations_kernel(const float* __restrict__ x, int64_t outer, int C, int64_t inner,
@@ -301,70 +297,50 @@ extern "C" int miseg_simplex_violations(void* stream, const float* x, int64_t ou
     return MISEG_OK;
 }
 
-extern "C" int64_t miseg_loss_ws_bytes(int64_t N, int64_t H, int64_t W) { return (int64_t)loss_blocks(N * H * W) * 4; }
+extern "C" int64_t miseg_loss_ws_bytes(int64_t N, int64_t H, int64_t W) { return (int64_t)pixel_blocks(N * H * W) * 4; }
 
-#define MISEG_DISPATCH_C(C, MACRO)                                                            \
-    switch (C) {                                                                              \
-        case 2: MACRO(2); break;                                                              \
-        case 3: MACRO(3); break;                                                              \
-        case 4: MACRO(4); break;                                                              \
-        case 5: MACRO(5); break;                                                              \
-        case 6: MACRO(6); break;                                                              \
-        case 8: MACRO(8); break;                                                              \
-        case 10: MACRO(10); break;                                                            \
-        case 16: MACRO(16); break;                                                            \
-        default: return fail(MISEG_E_INVALID, "unsupported class count %ld (2-6,8,10,16)", (long)C); \
-    }
+// What the four loss entry points do after their own null checks: the shape / workspace check, one streaming launch that leaves a
+// partial per block in ws -- launch(C as a std::integral_constant, blocks, stream, npix) --, and loss = scale * their sum.
+template <typename Launch>
+static int pixel_loss(const char* who, void* stream, int64_t N, int64_t H, int64_t W, int64_t C, float scale, float* loss, void* ws,
+                      int64_t ws_bytes, Launch&& launch) {
+    const int64_t npix = N * H * W;
+    MISEG_REQUIRE(npix > 0 && ws_bytes >= miseg_loss_ws_bytes(N, H, W), "%s: bad shape / workspace", who);
+    const int nb = pixel_blocks(npix);
+    hipStream_t st = as_stream(stream);
+#define L(CC) launch(std::integral_constant<int, CC>{}, nb, st, npix)
+    MISEG_DISPATCH_C(C, L)
+#undef L
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MISEG_E_LAUNCH, "%s_kernel: %s", who, hipGetErrorString(e));
+    return launch_finish_sum(st, (const float*)ws, nb, scale, loss);
+}
 
 extern "C" int miseg_softmax_kl(void* stream, const float* logits, const int64_t* labels, int64_t N, int64_t H, int64_t W, int64_t C,
                                 const float* upstream, float* loss, float* glogits, int32_t* bad_label, void* ws, int64_t ws_bytes) {
     MISEG_TAPE(miseg_softmax_kl, stream, logits, labels, N, H, W, C, upstream, loss, glogits, bad_label, ws, ws_bytes);
     MISEG_REQUIRE(logits && labels && loss && bad_label && ws, "softmax_kl: null pointer");
-    const int64_t npix = N * H * W;
-    MISEG_REQUIRE(npix > 0 && ws_bytes >= miseg_loss_ws_bytes(N, H, W), "softmax_kl: bad shape / workspace");
-    const int nb = loss_blocks(npix);
-    hipStream_t st = as_stream(stream);
-#define L(CC) hipLaunchKernelGGL(softmax_kl_kernel<CC>, dim3(nb), dim3(kLT), 0, st, logits, labels, npix, upstream, (float*)ws, glogits, bad_label)
-    MISEG_DISPATCH_C(C, L)
-#undef L
-    MISEG_LAUNCH_CHECK("softmax_kl_kernel");
-    hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nb, 1.0f / (float)npix, loss);
-    MISEG_LAUNCH_CHECK("finish_sum_kernel");
-    return MISEG_OK;
+    return pixel_loss("softmax_kl", stream, N, H, W, C, 1.0f / (float)(N * H * W), loss, ws, ws_bytes, [&](auto cc, int nb, hipStream_t st, int64_t npix) {
+        hipLaunchKernelGGL(softmax_kl_kernel<decltype(cc)::value>, dim3(nb), dim3(kLT), 0, st, logits, labels, npix, upstream, (float*)ws, glogits, bad_label);
+    });
 }
 
 extern "C" int miseg_softmax_mse(void* stream, const float* a, const float* b, const int32_t* flips, int64_t N, int64_t H, int64_t W,
                                  int64_t C, const float* upstream, float* loss, float* ga, void* ws, int64_t ws_bytes) {
     MISEG_TAPE(miseg_softmax_mse, stream, a, b, flips, N, H, W, C, upstream, loss, ga, ws, ws_bytes);
     MISEG_REQUIRE(a && b && loss && ws, "softmax_mse: null pointer");
-    const int64_t npix = N * H * W;
-    MISEG_REQUIRE(npix > 0 && ws_bytes >= miseg_loss_ws_bytes(N, H, W), "softmax_mse: bad shape / workspace");
-    const int nb = loss_blocks(npix);
-    hipStream_t st = as_stream(stream);
-#define L(CC) hipLaunchKernelGGL(softmax_mse_kernel<CC>, dim3(nb), dim3(kLT), 0, st, a, b, flips, (int)H, (int)W, npix, upstream, (float*)ws, ga)
-    MISEG_DISPATCH_C(C, L)
-#undef L
-    MISEG_LAUNCH_CHECK("softmax_mse_kernel");
-    hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nb, 1.0f / ((float)npix * (float)C), loss);
-    MISEG_LAUNCH_CHECK("finish_sum_kernel");
-    return MISEG_OK;
+    return pixel_loss("softmax_mse", stream, N, H, W, C, 1.0f / ((float)(N * H * W) * (float)C), loss, ws, ws_bytes, [&](auto cc, int nb, hipStream_t st, int64_t npix) {
+        hipLaunchKernelGGL(softmax_mse_kernel<decltype(cc)::value>, dim3(nb), dim3(kLT), 0, st, a, b, flips, (int)H, (int)W, npix, upstream, (float*)ws, ga);
+    });
 }
 
 extern "C" int miseg_softmax_klcons(void* stream, const float* a, const float* b, const int32_t* flips, int64_t N, int64_t H, int64_t W,
                                     int64_t C, const float* upstream, float* loss, float* ga, void* ws, int64_t ws_bytes) {
     MISEG_TAPE(miseg_softmax_klcons, stream, a, b, flips, N, H, W, C, upstream, loss, ga, ws, ws_bytes);
     MISEG_REQUIRE(a && b && loss && ws, "softmax_klcons: null pointer");
-    const int64_t npix = N * H * W;
-    MISEG_REQUIRE(npix > 0 && ws_bytes >= miseg_loss_ws_bytes(N, H, W), "softmax_klcons: bad shape / workspace");
-    const int nb = loss_blocks(npix);
-    hipStream_t st = as_stream(stream);
-#define L(CC) hipLaunchKernelGGL(softmax_klcons_kernel<CC>, dim3(nb), dim3(kLT), 0, st, a, b, flips, (int)H, (int)W, npix, upstream, (float*)ws, ga)
-    MISEG_DISPATCH_C(C, L)
-#undef L
-    MISEG_LAUNCH_CHECK("softmax_klcons_kernel");
-    hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nb, 1.0f / (float)npix, loss);
-    MISEG_LAUNCH_CHECK("finish_sum_kernel");
-    return MISEG_OK;
+    return pixel_loss("softmax_klcons", stream, N, H, W, C, 1.0f / (float)(N * H * W), loss, ws, ws_bytes, [&](auto cc, int nb, hipStream_t st, int64_t npix) {
+        hipLaunchKernelGGL(softmax_klcons_kernel<decltype(cc)::value>, dim3(nb), dim3(kLT), 0, st, a, b, flips, (int)H, (int)W, npix, upstream, (float*)ws, ga);
+    });
 }
 
 extern "C" int miseg_softmax_entropy(void* stream, const float* logits, int64_t N, int64_t H, int64_t W, int64_t C,
@@ -372,17 +348,9 @@ extern "C" int miseg_softmax_entropy(void* stream, const float* logits, int64_t 
     MISEG_TAPE(miseg_softmax_entropy, stream, logits, N, H, W, C, upstream, loss, glogits, ws, ws_bytes);
     MISEG_REQUIRE(logits && loss && ws, "softmax_entropy: null pointer");
     MISEG_REQUIRE(N >= 0 && H >= 0 && W >= 0, "softmax_entropy: bad shape");
-    const int64_t npix = N * H * W;
-    MISEG_REQUIRE(npix > 0 && ws_bytes >= miseg_loss_ws_bytes(N, H, W), "softmax_entropy: bad shape / workspace");
-    const int nb = loss_blocks(npix);
-    hipStream_t st = as_stream(stream);
-#define L(CC) hipLaunchKernelGGL(softmax_entropy_kernel<CC>, dim3(nb), dim3(kLT), 0, st, logits, npix, upstream, (float*)ws, glogits)
-    MISEG_DISPATCH_C(C, L)
-#undef L
-    MISEG_LAUNCH_CHECK("softmax_entropy_kernel");
-    hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nb, 1.0f / (float)npix, loss);
-    MISEG_LAUNCH_CHECK("finish_sum_kernel");
-    return MISEG_OK;
+    return pixel_loss("softmax_entropy", stream, N, H, W, C, 1.0f / (float)(N * H * W), loss, ws, ws_bytes, [&](auto cc, int nb, hipStream_t st, int64_t npix) {
+        hipLaunchKernelGGL(softmax_entropy_kernel<decltype(cc)::value>, dim3(nb), dim3(kLT), 0, st, logits, npix, upstream, (float*)ws, glogits);
+    });
 }
 
 extern "C" int miseg_flip(void* stream, const void* in, void* out, int64_t N, int64_t C, int64_t H, int64_t W,

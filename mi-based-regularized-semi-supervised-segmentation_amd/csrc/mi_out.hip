@@ -16,7 +16,7 @@
 //                    then the softmax backward on both sides; ga at (h,w) (optionally added to what is there: the consistency
 //                    gradient), gb at flip(h,w).  Every pixel is written exactly once: plain stores, no atomics.
 // All arithmetic fp32 on the VALU: at C = 4, pad = 1 a pixel costs ~300 FMA each way, far below the HBM time of its logits.
-#include "common.h"
+#include "pixel_loss.h"
 
 namespace miseg {
 
@@ -26,14 +26,6 @@ constexpr int kOT = 256;                 // threads per block
 constexpr int kTile = 16;                // 16 x 16 pixel tiles
 constexpr int kMaxPad = 3;
 constexpr int kMaxHS = kTile + 2 * kMaxPad;
-
-__device__ __forceinline__ void softmax_row(const float* __restrict__ z, int C, float* p) {
-    float mx = -3.4e38f;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); s += p[c]; }
-    for (int c = 0; c < C; ++c) p[c] = p[c] / s;
-}
 
 // the window of entry p, clamped to the image (a window list from elsewhere is trusted for its values, never for memory safety)
 __device__ __forceinline__ void load_window(const int32_t* __restrict__ win, int p, int H, int W, int& h0, int& h1, int& w0, int& w1) {
@@ -51,7 +43,7 @@ __device__ __forceinline__ void softmax_at(const float* __restrict__ z, int64_t 
     float v[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) v[c] = z[pix * C + c];
-    softmax_row(v, C, p);
+    softmax_c(v, C, p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- forward

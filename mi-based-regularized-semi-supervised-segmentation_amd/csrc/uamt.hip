@@ -11,17 +11,17 @@
 // load per row where C is a multiple of 4).  softmax_umse sums in two deterministic passes (per-block partials -> one finishing
 // block); the count K is an exact integer; the gradient's denominator is only known after the reduction, so the first pass stores
 // the unscaled gradient 2 p_c (d_c - <d, p>) (exactly 0 at a masked-out pixel) and a last launch multiplies it by
-// upstream / (C K + 1e-16), formed in double and rounded once.  Like ict.hip and dice.hip this unit carries its own copy of the small
-// helpers of losses.hip, which stays byte for byte what it was.  Built without contraction: the noise is one multiply, a clamp and one
-// add, and its normals are the bits of vat.hip's.
-#include "common.h"
+// upstream / (C K + 1e-16), formed in double and rounded once.  The softmax, the row loads, the pixel grid and the class-count dispatch
+// are those of pixel_loss.h, inline and so compiled under this unit's flags.  Built without contraction: the noise is one multiply, a
+// clamp and one add, and its normals are the bits of vat.hip's.
+#include "pixel_loss.h"
 #include "philox.h"
 
 namespace miseg {
 namespace uamt {
 
 constexpr int kT = 256;
-constexpr int kMaxBlocks = 2048;
+static_assert(kT == kPixelThreads, "pixel_blocks() counts blocks of kT pixels");
 
 // ---- the noisy copies -----------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float noisy(float x, float z, float sigma, float clip) {
@@ -51,39 +51,6 @@ __global__ __launch_bounds__(kT) void noise_add_kernel(const float* __restrict__
 }
 
 // ---- the pixel kernels ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void softmax_c(const float* __restrict__ z, int C, float* p) {
-    float mx = -3.4e38f;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); s += p[c]; }
-    for (int c = 0; c < C; ++c) p[c] = p[c] / s;
-}
-
-template <int C, bool V4>
-__device__ __forceinline__ void load_row(const float* __restrict__ p, float* z) {
-    if (V4) {
-#pragma unroll
-        for (int c = 0; c < C; c += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(p + c);
-            z[c] = v.x; z[c + 1] = v.y; z[c + 2] = v.z; z[c + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) z[c] = p[c];
-    }
-}
-
-template <int C, bool V4>
-__device__ __forceinline__ void store_row(float* __restrict__ p, const float* z) {
-    if (V4) {
-#pragma unroll
-        for (int c = 0; c < C; c += 4) *reinterpret_cast<float4*>(p + c) = make_float4(z[c], z[c + 1], z[c + 2], z[c + 3]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) p[c] = z[c];
-    }
-}
-
 template <int C, bool V4>
 __global__ __launch_bounds__(kT) void softmax_accum_kernel(const float* __restrict__ logits, int64_t npix, int first, float* __restrict__ acc) {
     for (int64_t i = blockIdx.x * (int64_t)kT + threadIdx.x; i < npix; i += (int64_t)gridDim.x * kT) {
@@ -227,22 +194,6 @@ __global__ __launch_bounds__(kT) void umse_scale_kernel(float* __restrict__ ga, 
     }
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static bool class_count_has_kernel(int64_t C) { return (C >= 2 && C <= 6) || C == 8 || C == 10 || C == 16; }
-static int pixel_blocks(int64_t npix) { return (int)std::min<int64_t>(cdiv(npix, kT), kMaxBlocks); }
-
-#define MISEG_UAMT_DISPATCH_C(C, MACRO)      \
-    switch (C) {                             \
-        case 2: MACRO(2, false); break;      \
-        case 3: MACRO(3, false); break;      \
-        case 4: if (v4) MACRO(4, true); else MACRO(4, false); break;   \
-        case 5: MACRO(5, false); break;      \
-        case 6: MACRO(6, false); break;      \
-        case 8: if (v4) MACRO(8, true); else MACRO(8, false); break;   \
-        case 10: MACRO(10, false); break;    \
-        default: if (v4) MACRO(16, true); else MACRO(16, false); break; \
-    }
-
 }  // namespace uamt
 }  // namespace miseg
 
@@ -255,7 +206,7 @@ extern "C" int miseg_noise_add(void* stream, const float* x, int64_t M, int64_t 
     MISEG_REQUIRE(M > 0 && passes >= 1 && M <= (1LL << 40) && passes <= (1LL << 20), "noise_add: empty input / bad shape");
     MISEG_REQUIRE(out + passes * M <= x || x + M <= out, "noise_add: out overlaps x");
     const int64_t total = passes * M;
-    const bool vec = M % 4 == 0 && uamt::aligned16(x) && uamt::aligned16(out);
+    const bool vec = M % 4 == 0 && aligned16(x) && aligned16(out);
     const dim3 grid((unsigned)std::min<int64_t>(cdiv(cdiv(total, 4), uamt::kT), 4096));
     if (vec) hipLaunchKernelGGL(uamt::noise_add_kernel<true>, grid, dim3(uamt::kT), 0, as_stream(stream), x, M, total, seed, sigma, clip, out);
     else hipLaunchKernelGGL(uamt::noise_add_kernel<false>, grid, dim3(uamt::kT), 0, as_stream(stream), x, M, total, seed, sigma, clip, out);
@@ -266,14 +217,14 @@ extern "C" int miseg_noise_add(void* stream, const float* x, int64_t M, int64_t 
 extern "C" int miseg_softmax_accum(void* stream, const float* logits, int64_t N, int64_t H, int64_t W, int64_t C, int first, float* acc) {
     MISEG_TAPE(miseg_softmax_accum, stream, logits, N, H, W, C, first, acc);
     MISEG_REQUIRE(logits && acc, "softmax_accum: null pointer");
-    MISEG_REQUIRE(uamt::class_count_has_kernel(C), "softmax_accum: unsupported class count %ld (2-6,8,10,16)", (long)C);
+    MISEG_REQUIRE(class_count_has_kernel(C), "softmax_accum: unsupported class count %ld (2-6,8,10,16)", (long)C);
     MISEG_REQUIRE(N > 0 && H > 0 && W > 0 && N < (1LL << 31), "softmax_accum: empty batch / bad shape");
     const int64_t npix = N * H * W;
-    const int nb = uamt::pixel_blocks(npix);
-    const bool v4 = C % 4 == 0 && uamt::aligned16(logits) && uamt::aligned16(acc);
+    const int nb = pixel_blocks(npix);
+    const bool v4 = C % 4 == 0 && aligned16(logits) && aligned16(acc);
     hipStream_t st = as_stream(stream);
 #define L(CC, VV) hipLaunchKernelGGL((uamt::softmax_accum_kernel<CC, VV>), dim3(nb), dim3(uamt::kT), 0, st, logits, npix, first, acc)
-    MISEG_UAMT_DISPATCH_C(C, L)
+    MISEG_DISPATCH_C_V4(C, v4, L)
 #undef L
     MISEG_LAUNCH_CHECK("softmax_accum_kernel");
     return MISEG_OK;
@@ -281,7 +232,7 @@ extern "C" int miseg_softmax_accum(void* stream, const float* logits, int64_t N,
 
 extern "C" int64_t miseg_softmax_umse_ws_bytes(int64_t N, int64_t H, int64_t W) {
     if (N <= 0 || H <= 0 || W <= 0) return 0;
-    return (int64_t)uamt::pixel_blocks(N * H * W) * 16 + 16;
+    return (int64_t)pixel_blocks(N * H * W) * 16 + 16;
 }
 
 extern "C" int miseg_softmax_umse(void* stream, const float* a, const float* b, const float* acc, int64_t N, int64_t H, int64_t W, int64_t C,
@@ -289,24 +240,24 @@ extern "C" int miseg_softmax_umse(void* stream, const float* a, const float* b, 
                                   float* stats, void* ws, int64_t ws_bytes) {
     MISEG_TAPE(miseg_softmax_umse, stream, a, b, acc, N, H, W, C, inv_passes, thr, upstream, loss, ga, kept, stats, ws, ws_bytes);
     MISEG_REQUIRE(a && b && acc && thr && loss && ws, "softmax_umse: null pointer");
-    MISEG_REQUIRE(uamt::class_count_has_kernel(C), "softmax_umse: unsupported class count %ld (2-6,8,10,16)", (long)C);
+    MISEG_REQUIRE(class_count_has_kernel(C), "softmax_umse: unsupported class count %ld (2-6,8,10,16)", (long)C);
     MISEG_REQUIRE(N > 0 && H > 0 && W > 0 && N < (1LL << 31), "softmax_umse: empty batch / bad shape");
     const int64_t need = miseg_softmax_umse_ws_bytes(N, H, W);
     MISEG_REQUIRE(ws_bytes >= need && ((uintptr_t)ws & 7) == 0, "softmax_umse: workspace of %ld bytes (8-byte aligned), %ld needed", (long)ws_bytes,
                   (long)need);
     const int64_t npix = N * H * W;
-    const int nb = uamt::pixel_blocks(npix);
-    const bool v4 = C % 4 == 0 && uamt::aligned16(a) && uamt::aligned16(b) && uamt::aligned16(acc) && (!ga || uamt::aligned16(ga));
+    const int nb = pixel_blocks(npix);
+    const bool v4 = C % 4 == 0 && aligned16(a) && aligned16(b) && aligned16(acc) && (!ga || aligned16(ga));
     hipStream_t st = as_stream(stream);
 #define L(CC, VV) hipLaunchKernelGGL((uamt::umse_kernel<CC, VV>), dim3(nb), dim3(uamt::kT), 0, st, a, b, acc, npix, inv_passes, thr, ws, ga)
-    MISEG_UAMT_DISPATCH_C(C, L)
+    MISEG_DISPATCH_C_V4(C, v4, L)
 #undef L
     MISEG_LAUNCH_CHECK("umse_kernel");
     hipLaunchKernelGGL(uamt::umse_finish_kernel, dim3(1), dim3(256), 0, st, ws, nb, npix, (int)C, upstream, loss, (long long*)kept, stats);
     MISEG_LAUNCH_CHECK("umse_finish_kernel");
     if (ga) {
         const int64_t numel = npix * C;
-        const bool vec = numel % 4 == 0 && uamt::aligned16(ga);
+        const bool vec = numel % 4 == 0 && aligned16(ga);
         const int64_t units = vec ? numel / 4 : numel;
         const dim3 grid((unsigned)std::min<int64_t>(cdiv(units, uamt::kT), 4096));
         const float* gscale = uamt::Workspace(ws, nb).gscale;

@@ -206,7 +206,7 @@ def softmax_umse(a: Tensor, b: Tensor, acc: Tensor, thr: Tensor, passes: int):
     return loss, box[0], box[1]
 
 
-_LOSS_CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)     # MISEG_DISPATCH_C of csrc/losses.hip
+_LOSS_CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)     # MISEG_DISPATCH_C of csrc/pixel_loss.h
 
 
 def softmax_entropy_supported(c: int) -> bool:

@@ -18,7 +18,7 @@ import synth
 F64 = torch.float64
 EPS = 1e-16
 
-# ---- the launchers' constants (csrc/losses.hip: kLT, loss_blocks, MISEG_DISPATCH_C, the grids of argmax_dice / cat_flip*; csrc/tape.hip: copy_blocks)
+# ---- the launchers' constants (csrc/pixel_loss.h: pixel_blocks, MISEG_DISPATCH_C; csrc/losses.hip: kLT, the grids of argmax_dice / cat_flip*; csrc/tape.hip: copy_blocks)
 LOSS_THREADS = 256
 LOSS_MAX_BLOCKS = 2048
 CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)

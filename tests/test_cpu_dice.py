@@ -167,10 +167,14 @@ def test_refusals_need_no_gpu():
 def test_supported_class_counts_mirror_the_dispatch_list():
     from miseg_amd import ops
     assert [c for c in range(0, 40) if ops.softmax_dice_supported(c)] == list(DISPATCH)
+    # ... the list of the one switch of the pixel-loss units, which every variant of the Dice launches goes through
     src = open(os.path.join(PKG, "csrc", "dice.hip")).read()
-    macro = src[src.index("#define MISEG_DICE_DISPATCH"):]
-    macro = macro[:macro.index("#define MISEG_DICE_VARIANT")]
-    assert tuple(int(m) for m in re.findall(r"MACRO\((\d+),", macro)) == DISPATCH
+    variant = src[src.index("#define MISEG_DICE_VARIANT"):src.index('extern "C" int miseg_softmax_dice(')]
+    assert variant.count("MISEG_DISPATCH_C(C, MACRO, ") == 4 and "switch" not in src
+    shared = open(os.path.join(PKG, "csrc", "pixel_loss.h")).read()
+    macro = shared[shared.index("#define MISEG_DISPATCH_C"):]
+    macro = macro[:macro.index("default:")]
+    assert tuple(int(m) for m in re.findall(r"case (\d+):", macro)) == DISPATCH
 
 
 # ---------------------------------------------------------------------------------------------------------------- configuration

@@ -8,7 +8,7 @@ import trainer_harness as th
 from trainer_harness import PKG, ROOT
 
 NEW = "miseg_softmax_entropy"
-DISPATCH = (2, 3, 4, 5, 6, 8, 10, 16)          # MISEG_DISPATCH_C of csrc/losses.hip
+DISPATCH = (2, 3, 4, 5, 6, 8, 10, 16)          # MISEG_DISPATCH_C of csrc/pixel_loss.h
 
 
 def test_trainer_zoo_has_entmin_reading_its_section():
@@ -48,8 +48,9 @@ def test_library_exports_and_header_declares_the_new_entry_point():
 def test_supported_class_counts_mirror_the_dispatch_list():
     from miseg_amd import ops
     assert [c for c in range(0, 40) if ops.softmax_entropy_supported(c)] == list(DISPATCH)
-    # ... which is the list the library's source dispatches on
-    src = open(os.path.join(PKG, "csrc", "losses.hip")).read()
+    # ... which is the list the library's source dispatches on: the one switch of the pixel-loss units, which the entry point's unit uses
+    assert "MISEG_DISPATCH_C(C, L)" in open(os.path.join(PKG, "csrc", "losses.hip")).read()
+    src = open(os.path.join(PKG, "csrc", "pixel_loss.h")).read()
     macro = src[src.index("#define MISEG_DISPATCH_C"):]
     macro = macro[:macro.index("default:")]
     assert tuple(int(m) for m in re.findall(r"case (\d+):", macro)) == DISPATCH

@@ -120,9 +120,13 @@ def test_the_tables_mirror_the_launchers_constants():
     from miseg_amd import _cabi
     csrc = os.path.join(_cabi.PKG_ROOT, "csrc")
     losses, tape = open(os.path.join(csrc, "losses.hip")).read(), open(os.path.join(csrc, "tape.hip")).read()
-    assert int(re.search(r"constexpr int kLT = (\d+);", losses).group(1)) == P.LOSS_THREADS
-    assert int(re.search(r"loss_blocks\(int64_t npix\) \{ return \(int\)std::min<int64_t>\(cdiv\(npix, kLT\), (\d+)\)", losses).group(1)) == P.LOSS_MAX_BLOCKS
-    dispatch = losses[losses.index("#define MISEG_DISPATCH_C"):losses.index("default: return fail")]
+    shared = open(os.path.join(csrc, "pixel_loss.h")).read()          # the pixel grid and the class-count dispatch of every pixel-loss unit
+    assert int(re.search(r"constexpr int kLT = (\d+);", losses).group(1)) == P.LOSS_THREADS and "static_assert(kLT == kPixelThreads" in losses
+    assert int(re.search(r"constexpr int kPixelThreads = (\d+);", shared).group(1)) == P.LOSS_THREADS
+    assert int(re.search(r"pixel_blocks\(int64_t npix\) \{ return \(int\)std::min<int64_t>\(cdiv\(npix, kPixelThreads\), (\d+)\)", shared).group(1)) == P.LOSS_MAX_BLOCKS
+    assert "miseg_loss_ws_bytes(int64_t N, int64_t H, int64_t W) { return (int64_t)pixel_blocks(N * H * W) * 4; }" in losses
+    assert "#define MISEG_DISPATCH_C" not in losses and losses.count("const int nb = pixel_blocks(npix);") == 1
+    dispatch = shared[shared.index("#define MISEG_DISPATCH_C"):shared.index("default: return fail")]
     assert tuple(int(v) for v in re.findall(r"case (\d+):", dispatch)) == P.CLASS_COUNTS
     assert f"cdiv(H * W, {P.DICE_THREADS}), {P.DICE_MAX_BLOCKS})" in losses
     assert losses.count(f"cdiv(total, {P.CAT_THREADS}), {P.CAT_MAX_BLOCKS})") == 3          # cat_flip, cat_flip_pad, cat_flipped
