@@ -781,6 +781,23 @@ int64_t miseg_softmax_umse_ws_bytes(int64_t N, int64_t H, int64_t W);
 int miseg_softmax_umse(void* stream, const float* a, const float* b, const float* acc, int64_t N, int64_t H, int64_t W, int64_t C,
                        float inv_passes, const float* thr, const float* upstream, float* loss, float* ga, int64_t* kept, float* stats,
                        void* ws, int64_t ws_bytes);
+/* Cross pseudo supervision (Trainer.name=cps; Chen et al., CVPR 2021, no counterpart in the reference: DESIGN.md section 30;
+ * csrc/cps.hip, library version 419).  Two networks' fp32 NHWC logits a and b, each held to the other's hard prediction.  Per pixel
+ * ya = argmax_c a_c, yb = argmax_c b_c (the lowest index wins a tie; +0.0 and -0.0 tie), labels detached;
+ *   loss[0] = cps_a = mean_pix (logsumexp(a) - a[yb]),   loss[1] = cps_b = mean_pix (logsumexp(b) - b[ya])   (no epsilon),
+ *   ga = upstream (softmax(a) - e_yb) / npix,             gb = upstream (softmax(b) - e_ya) / npix,            npix = N H W,
+ *   agree = int64[1], the number of pixels with ya == yb.
+ * upstream (device fp32[1]), ga, gb and agree may each be NULL; loss[0] and loss[1] are always written, so with only ga given the
+ * call is the one-sided pseudo-label loss of a against b.  Two launches: one pass that reads a and b once, writes the gradients
+ * and leaves per-block partials (two sums, an exact integer count), and one finishing block that adds them in a fixed order in
+ * double.  No atomics: deterministic, and the loss bits do not depend on which optional outputs are asked for.  A NaN or +inf
+ * logit, or -inf at a pixel's label, makes the loss non-finite; nothing else is promised about a pixel with one.
+ * ws: miseg_softmax_cross_pseudo_ws_bytes(N, H, W) bytes, 8-byte aligned.
+ * Refusals (MISEG_E_INVALID, nothing launched, nothing written): a class count outside 2-6, 8, 10, 16, an empty batch, a short or
+ * misaligned workspace, a NULL a / b / loss / ws, ga or gb overlapping a, b or each other. */
+int64_t miseg_softmax_cross_pseudo_ws_bytes(int64_t N, int64_t H, int64_t W);
+int miseg_softmax_cross_pseudo(void* stream, const float* a, const float* b, int64_t N, int64_t H, int64_t W, int64_t C,
+                               const float* upstream, float* loss, float* ga, float* gb, int64_t* agree, void* ws, int64_t ws_bytes);
 /* Overflow test of the half-precision modes (BASELINE configs[4]: torch.cuda.amp-style loss scaling; the reference itself trains in
  * fp32 and has no such step): count[0] = number of non-finite entries of grad[0..numel), as a float (0 = clean).  The caller appends
  * it to the guard flags of miseg_adam_step_guarded -- an overflowed gradient then moves neither parameters nor moments -- and the

@@ -15,7 +15,7 @@ int fail(int code, const char* fmt, ...) {
 }
 }  // namespace miseg_core
 
-extern "C" int miseg_version(void) { return 418; }   // round 4 (profiles/r04_pmc.json is keyed by 406) + miseg_softmax_entropy (407) + csrc/contrast.hip (408) + csrc/contrast_decoder.hip: miseg_bias_lrelu_*, miseg_bias_amaxpool_* (409) + csrc/surface.hip: miseg_surface_stats (410) + miseg_softmax_kl zeroes the gradient of a pixel with a bad label (411) + csrc/affine.hip: miseg_affine_warp_fwd/bwd (412) + csrc/components.hip: miseg_largest_component (413) + miseg_conv3x3_stem_dgrad, csrc/vat.hip: miseg_l2_perturb, miseg_normal_fill (414) + miseg_radam_step, miseg_adabound_step (415) + csrc/dice.hip: miseg_softmax_dice (416) + csrc/ict.hip: miseg_cat_mixed, miseg_softmax_mix_mse, miseg_softmax_mix_klcons (417) + csrc/uamt.hip: miseg_noise_add, miseg_softmax_accum, miseg_softmax_umse (418)
+extern "C" int miseg_version(void) { return 419; }   // round 4 (profiles/r04_pmc.json is keyed by 406) + miseg_softmax_entropy (407) + csrc/contrast.hip (408) + csrc/contrast_decoder.hip: miseg_bias_lrelu_*, miseg_bias_amaxpool_* (409) + csrc/surface.hip: miseg_surface_stats (410) + miseg_softmax_kl zeroes the gradient of a pixel with a bad label (411) + csrc/affine.hip: miseg_affine_warp_fwd/bwd (412) + csrc/components.hip: miseg_largest_component (413) + miseg_conv3x3_stem_dgrad, csrc/vat.hip: miseg_l2_perturb, miseg_normal_fill (414) + miseg_radam_step, miseg_adabound_step (415) + csrc/dice.hip: miseg_softmax_dice (416) + csrc/ict.hip: miseg_cat_mixed, miseg_softmax_mix_mse, miseg_softmax_mix_klcons (417) + csrc/uamt.hip: miseg_noise_add, miseg_softmax_accum, miseg_softmax_umse (418) + csrc/cps.hip: miseg_softmax_cross_pseudo (419)
 extern "C" const char* miseg_last_error(void) { return miseg::last_error_buf(); }
 
 // ---- cross-stream ordering without a system-scope fence --------------------------------------------------------------------------

@@ -41,7 +41,24 @@ __device__ __forceinline__ void store_row(float* __restrict__ p, const float* z)
     }
 }
 
-constexpr int kPixelThreads = 256;      // the block size of every pixel kernel (kLT, kDT, kT of the units)
+// exact integer block sum (fixed order over the waves): the counts of uamt.hip and cps.hip
+__device__ __forceinline__ long long block_sum_i64(long long v, long long* red /* >= 17 words of LDS */) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long t = 0;
+        for (int i = 0; i < nw; ++i) t += red[i];
+        red[16] = t;
+    }
+    __syncthreads();
+    return red[16];
+}
+
+constexpr int kPixelThreads = 256;     // the block size of every pixel kernel (kLT, kDT, kT of the units)
 static inline int pixel_blocks(int64_t npix) { return (int)std::min<int64_t>(cdiv(npix, kPixelThreads), 2048); }
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static inline bool class_count_has_kernel(int64_t C) { return (C >= 2 && C <= 6) || C == 8 || C == 10 || C == 16; }

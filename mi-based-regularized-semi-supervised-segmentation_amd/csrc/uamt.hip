@@ -66,23 +66,6 @@ __global__ __launch_bounds__(kT) void softmax_accum_kernel(const float* __restri
     }
 }
 
-// exact integer block sum (fixed order over the waves)
-__device__ __forceinline__ long long block_sum_i64(long long v, long long* red /* >= 17 words of LDS */) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int i = 0; i < nw; ++i) t += red[i];
-        red[16] = t;
-    }
-    __syncthreads();
-    return red[16];
-}
-
 // The workspace: K partials (int64 [nb]) | masked squared-distance partials (fp32 [nb]) | uncertainty partials (fp32 [nb]) | the
 // gradient's scale (fp32 [1]).
 struct Workspace {

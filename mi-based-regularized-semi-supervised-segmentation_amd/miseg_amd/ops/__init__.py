@@ -23,7 +23,7 @@ from .contrast import (_CD_MAX_C, _SUPCON_MAX_D, _SUPCON_MAX_N, avgpool_nhwc, bi
                        bias_lrelu_supported, conv3x3_bias, conv3x3_bias_supported, supcon, supcon_supported)
 from .heads import global_head, global_head_var, local_head, local_head_var  # noqa: E402,F401
 from .losses import (_LOSS_CLASS_COUNTS, softmax_dice, softmax_dice_supported, softmax_entropy, softmax_entropy_supported, softmax_kl,  # noqa: E402,F401
-                     softmax_accum, softmax_kl_consistency, softmax_mix_kl_consistency, softmax_mix_mse, softmax_mse, softmax_umse)
+                     softmax_accum, softmax_cross_pseudo, softmax_kl_consistency, softmax_mix_kl_consistency, softmax_mix_mse, softmax_mse, softmax_umse)
 from .metrics import argmax_dice, largest_component, surface_stats  # noqa: E402,F401
 from .mi import (LOCAL_LOSS_SINGLE_BLOCK_MAX_K, MI_PRECISIONS, _local_loss, colour_windows, global_joint, global_mi, global_mi_pair,  # noqa: E402,F401
                  local_mi_heads, local_mi_losses, local_mi_raw_joint, mi_precision_code, mi_precision_name, output_local_mi,

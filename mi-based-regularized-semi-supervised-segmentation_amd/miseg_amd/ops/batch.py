@@ -182,12 +182,23 @@ def _split_part_of(given: Tensor, used: Tensor):
 
 def _scaled_grad(part, grad: Tensor, g: Tensor) -> Tensor:
     """``grad * g`` for a 0-d upstream gradient ``g``; for a part of a split_rows, written into the part's rows of the batch
-    gradient by one library launch (scale read from device memory) and returned as that view."""
+    gradient by one library launch (scale read from device memory) and returned as that view.  Where another loss's backward has
+    written those rows already in this pass (two losses on one part: the supervised and the cross term of ``cps``), the product is
+    ADDED to them -- two library launches -- and None is returned: autograd holds the rows as the first loss's gradient, whichever
+    of the two ran first.  Precondition: every gradient of such a part comes through this function (or ``output_local_mi``'s backward,
+    which adds into the rows the same way).  A further consumer that hands autograd an ORDINARY tensor for the part would let it form
+    ``rows + tensor`` in a new buffer, possibly before a later in-place addition, which would then be lost; no shipped trainer has one."""
     if part is not None and g.dim() == 0 and g.dtype == torch.float32 and g.is_cuda and grad.dtype == torch.float32 and grad.numel() % 4 == 0:
         holder, idx = part
         dst = holder.rows(idx)
         # (the launch stores 16-byte vectors: rows that start off such a boundary -- odd map sizes -- take the torch product below)
-        if dst.dtype == grad.dtype and dst.shape == grad.shape and dst.stride() == grad.stride() and dst.data_ptr() % 16 == 0:
+        if dst.dtype == grad.dtype and dst.shape == grad.shape and dst.stride() == grad.stride() and dst.data_ptr() % 16 == 0 and \
+                grad.data_ptr() % 16 == 0:
+            if idx in holder.filled:
+                scaled = torch.empty_like(grad)
+                call("miseg_assemble_rows", _stream(), _ptr(scaled), _ptr(grad), _ptr(g), grad.numel(), None, None, 0, None, None, 0)
+                call("miseg_axpy", _stream(), 0, _ptr(scaled), _ptr(dst), grad.numel())
+                return None
             call("miseg_assemble_rows", _stream(), _ptr(dst), _ptr(grad), _ptr(g), grad.numel(), None, None, 0, None, None, 0)
             holder.filled.add(idx)
             return dst

@@ -1,4 +1,4 @@
-"""Pixel-wise losses on the logits (csrc/losses.hip, dice.hip, ict.hip, uamt.hip): each is one fused kernel that also leaves the gradient of the
+"""Pixel-wise losses on the logits (csrc/losses.hip, dice.hip, ict.hip, uamt.hip, cps.hip): each is one fused kernel that also leaves the gradient of the
 logits, which the backward only has to scale."""
 from __future__ import annotations
 
@@ -204,6 +204,84 @@ def softmax_umse(a: Tensor, b: Tensor, acc: Tensor, thr: Tensor, passes: int):
     box: list = []
     loss = _SoftmaxUMSE.apply(a, b, acc, thr, int(passes), box)
     return loss, box[0], box[1]
+
+
+def _cps_operand(x, name: str):
+    """One operand of ``softmax_cross_pseudo``: ``(tensors, rows, nhwc)`` -- the tensors autograd sees, their row counts and the fp32
+    NHWC batch the kernel reads (``nhwc[i]``: the i-th tensor's rows of it).  A tensor is read in place when it is fp32 NHWC already
+    and converted in layout otherwise; a sequence must be the parts of one ``split_rows`` in order, adjacent in memory."""
+    parts = tuple(x) if isinstance(x, (tuple, list)) else (x,)
+    for t in parts:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4):
+            raise TypeError(f"softmax_cross_pseudo: {name} must be fp32 [N,C,H,W] logits on the GPU (there is no torch fallback), got "
+                            f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')}")
+    if len(parts) == 1:
+        nhwc = logits_nhwc(parts[0])
+        return parts, [int(parts[0].shape[0])], [nhwc]
+    nhwc = [logits_nhwc(t) for t in parts]
+    for prev, t, given in zip(nhwc, nhwc[1:], parts[1:]):
+        if t.data_ptr() != given.data_ptr() or t.shape[1:] != prev.shape[1:] or t.data_ptr() != prev.data_ptr() + 4 * prev.numel():
+            raise TypeError(f"softmax_cross_pseudo: the parts of {name} must be adjacent fp32 NHWC rows of one batch (ops.split_rows)")
+    return parts, [int(t.shape[0]) for t in parts], nhwc
+
+
+class _SoftmaxCrossPseudo(torch.autograd.Function):
+    """Two differentiable operands, each one tensor or the parts of a split_rows: ``ctx.groups[k]`` holds, per tensor of operand k, its
+    place in a split_rows (if any), its first row and its row count in the saved gradient."""
+
+    @staticmethod
+    def forward(ctx, box: list, agree_out: Optional[Tensor], na: int, *tensors: Tensor):
+        given = (tensors[:na], tensors[na:])
+        read, ctx.groups, wants = [], [], []
+        for k, (name, group) in enumerate(zip("ab", given)):
+            parts, rows, nhwc = _cps_operand(group if len(group) > 1 else group[0], name)
+            read.append((nhwc[0], sum(rows)))
+            ctx.groups.append([(_split_part_of(t, u), sum(rows[:i]), rows[i]) for i, (t, u) in enumerate(zip(parts, nhwc))])
+            first = 3 + (0 if k == 0 else na)
+            wants.append(any(ctx.needs_input_grad[first:first + len(parts)]))
+        (a, n), (b, nb) = read
+        _, c, h, w = a.shape
+        if nb != n or b.shape[1:] != a.shape[1:]:
+            raise ValueError(f"softmax_cross_pseudo: a has {n} x {tuple(a.shape[1:])} logits and b {nb} x {tuple(b.shape[1:])}")
+        dev = a.device
+        loss = scalar_out((2,), dev)
+        grads = [empty_nhwc(n, c, h, w, torch.float32, dev) if want else None for want in wants]
+        agree = _kept_out(dev) if agree_out is None else agree_out
+        assert agree.dtype == torch.int64 and agree.numel() == 1 and agree.data_ptr() % 8 == 0, (agree.dtype, agree.shape)
+        ws = _ws(query("miseg_softmax_cross_pseudo_ws_bytes", n, h, w), dev)
+        call("miseg_softmax_cross_pseudo", _stream(), _ptr(a), _ptr(b), n, h, w, c, None, _ptr(loss), _ptr(grads[0]), _ptr(grads[1]), _ptr(agree),
+             _ptr(ws), ws.numel())
+        ctx.wants = wants
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        box.append(agree)         # handed over beside the graph, as the flag of _SoftmaxKL
+        return loss
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        saved = list(ctx.saved_tensors)
+        out = []
+        for k, group in enumerate(ctx.groups):
+            grad = saved.pop(0) if ctx.wants[k] else None
+            for part, first, rows in group:
+                out.append(None if grad is None else _scaled_grad(part, grad if len(group) == 1 else grad.narrow(0, first, rows), g[k]))
+        return (None, None, None) + tuple(out)
+
+
+def softmax_cross_pseudo(a, b, agree_out: Optional[Tensor] = None):
+    """The cross pseudo supervision term of two networks' logits, one fused kernel with both gradients: with
+    ``ya = argmax(a, 1)`` and ``yb = argmax(b, 1)`` (first maximum, labels detached), ``loss = [cross_entropy(a, yb),
+    cross_entropy(b, ya)]`` as means over the pixels, and ``agree`` = int64 [1], the number of pixels with ``ya == yb``.  Returns
+    ``(loss, agree)``; ``LinearLoss.of(loss)`` is the sum of the two.  The backward scales the saved gradient of ``a`` by the upstream
+    gradient of ``loss[0]`` and that of ``b`` by ``loss[1]``'s.  An operand is one [N,C,H,W] tensor -- it may be a part of a
+    ``split_rows`` -- or the sequence of all adjacent parts of one, read as the batch they make: each part's gradient then goes to its
+    own rows.  Under ``torch.no_grad()`` or for an operand that needs none, that gradient is not computed.  fp32 logits on the device
+    only: anything else raises ``TypeError``.  ``agree_out``: where to write the count (int64 [1], 8-byte aligned) instead of the
+    iteration's counter pair."""
+    ta = tuple(a) if isinstance(a, (tuple, list)) else (a,)
+    tb = tuple(b) if isinstance(b, (tuple, list)) else (b,)
+    box: list = []
+    loss = _SoftmaxCrossPseudo.apply(box, agree_out, len(ta), *ta, *tb)
+    return loss, box[0]
 
 
 _LOSS_CLASS_COUNTS = (2, 3, 4, 5, 6, 8, 10, 16)     # MISEG_DISPATCH_C of csrc/pixel_loss.h

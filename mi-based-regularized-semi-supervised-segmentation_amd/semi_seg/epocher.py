@@ -159,6 +159,9 @@ class _Pending:
             fields = ticket.io.wait(ticket)
             vals = fields["scalars"].tolist()
             out = dict(zip(ticket.names, vals))
+            for name, field in fields.items():        # what an epocher put into the block beside the standard fields (cps: "agree")
+                if name not in ("scalars", "inter", "union", "nonfinite"):
+                    out[name] = field.tolist()
             checks.raise_failed(ticket.items, vals[len(ticket.names):len(ticket.names) + len(ticket.items)])
             extras = [fields["inter"], fields["union"]]
             if "nonfinite" in fields:
@@ -341,6 +344,7 @@ class TrainEpocher(_num_class_mixin, _Epocher):
         seed = random.randint(0, int(1e7))
         labeled_image, labeled_target, _, _, label_group = self._unzip_data(labeled_data, self._device)
         unlabeled_image, _unlabeled_target, *_ = self._unzip_data(unlabeled_data, self._device)
+        self._batch_shapes = (tuple(labeled_image.shape), tuple(unlabeled_image.shape))
         flip_masks = self._draw_words(seed, len(unlabeled_image))
         self._seed = seed
         io = self._io_for(labeled_image.device)
@@ -536,10 +540,13 @@ class TrainEpocher(_num_class_mixin, _Epocher):
             )
         return self._finish_step(sup_loss, reg_loss, label_logits, labels)
 
-    def _finish_step(self, sup_loss, reg_loss, label_logits: Tensor, labels: Tensor):
+    def _finish_step(self, sup_loss, reg_loss, label_logits: Tensor, labels: Tensor, more_loss=None):
         """The iteration's tail: the total loss, the forward read-back, backward, the guarded optimiser launch.  Returns the Dice
-        counts."""
+        counts.  ``more_loss``: a term of the total that is neither reported as ``sup_loss`` nor weighted (a second network's
+        supervised loss)."""
         total_loss = sup_loss + self._reg_weight * reg_loss
+        if more_loss is not None:
+            total_loss = total_loss + more_loss
         # Everything the read-back needs from the FORWARD pass is launched here, before backward: the Dice counts and the iteration's
         # report (meter values + the simplex / NaN flags that guard the update).  Issued after backward they sat behind the optimiser's
         # wait for the weight-gradient stream, i.e. on the step's tail (~19 us); here they run while the main stream waits for the IIC chain.
@@ -1084,6 +1091,87 @@ class UAMTEpocher(MeanTeacherEpocher):
     def _record(self, host: dict, inter: Tensor, union: Tensor, label_group) -> None:
         super()._record(host, inter, union, label_group)
         self.meters["threshold"].add(self._thr_sent.pop(0))       # records arrive in the order of the iterations
+
+
+class CPSEpocher(TrainEpocher):
+    """``cps``: cross pseudo supervision (Chen et al., CVPR 2021; ``CPSParameters``) -- two trainable networks
+    with different initial weights, each held to the other's hard prediction.  One iteration:
+
+    1. the seed is drawn as in every epocher (the host RNG stream stays aligned) and otherwise unused; no flips are drawn or applied,
+       the flips slot of the step block holds UB zeros;
+    2. ``x = [labeled | unlabeled]``, assembled once (one launch) and fed to both networks;
+    3. two training forwards with autograd, ``a = model(x)`` and ``b = model_b(x)``: each in train mode with its own batch statistics
+       and running statistics; the ``FeatureExtractor`` stays on ``model``;
+    4. ``sup_a`` and ``sup_b``: the supervised criterion on each network's labeled rows;
+    5. the cross term (``ops.softmax_cross_pseudo``, one launch) over all rows -- with ``on_labeled`` false over the unlabeled rows
+       only --: ``cps_a = mean_px CE(a, argmax b)``, ``cps_b = mean_px CE(b, argmax a)``, labels detached, ``reg_loss = cps_a + cps_b``;
+    6. ``sup_a + sup_b + reg_weight * reg_loss``, one backward, the guarded fused optimiser over BOTH networks' parameters (one flat
+       buffer): a skipped iteration moves neither network.
+
+    Meters beside ``TrainEpocher``'s: ``sup_loss`` is network A's, ``sup_loss_b`` network B's, ``agreement`` the exact share of the
+    term's pixels where the two hard predictions coincide, ``reg_weight``; ``sup_dice`` is network A's.  The term has no
+    data-dependent denominator, so data-parallel runs need nothing beyond the gradient all-reduce."""
+
+    _TRAIN_FORWARDS = 2
+    METERS = ("sup_loss_b", "agreement", "reg_weight")
+
+    def __init__(self, model, model_b, optimizer, labeled_loader: T_loader, unlabeled_loader: T_loader, sup_criterion: T_loss,
+                 reg_weight: float, num_batches: int, cur_epoch=0, device="cpu", feature_position=None, feature_importance=None,
+                 on_labeled: bool = True) -> None:
+        super().__init__(model, optimizer, labeled_loader, unlabeled_loader, sup_criterion, reg_weight, num_batches, cur_epoch, device,
+                         feature_position, feature_importance)
+        if float(reg_weight) < 0.0:
+            raise ValueError(f"CPSEpocher: the weight of the cross term must not be negative, got {reg_weight}")
+        self._model_b = model_b
+        self._on_labeled = bool(on_labeled)
+        self._pixels_sent: List[int] = []          # pixels of the cross term, of the iterations whose read-back is still under way
+
+    def _run(self, *args, **kwargs) -> EpochResultDict:
+        self._model_b.train()
+        self.meters["reg_weight"].add(self._reg_weight)
+        return super()._run(*args, **kwargs)
+
+    def _draw_words(self, seed: int, ub: int) -> List[int]:
+        (lb, _, h, w), _ = self._batch_shapes
+        self._pixels_sent.append(((lb if self._on_labeled else 0) + ub) * h * w)
+        return [0] * ub
+
+    def _stage(self, io, flip_masks) -> int:
+        if not hasattr(self._optimizer, "host_step"):
+            raise RuntimeError("Trainer.name=cps needs a fused optimiser (Optim.name: Adam, RAdam, AdaBound or AdaBoundW)")
+        return super()._stage(io, flip_masks)
+
+    def _tape_signature(self):
+        buf = next(iter(self._model_b.buffers()), None)
+        return super()._tape_signature() + (id(self._model_b), None if buf is None else buf.data_ptr(), self._on_labeled)
+
+    def _device_step(self, labeled_image: Tensor, labeled_target: Tensor, unlabeled_image: Tensor, flips2: Tensor, seed: int = None):
+        lb, ub = len(labeled_image), len(unlabeled_image)
+        self._flips2 = flips2
+        batch = self._assemble(labeled_image, unlabeled_image, flips2[:ub], keep_unflipped=False)      # zero flips: the plain concatenation
+        logits_a = self._forward(batch, ub)
+        with checks.deferred(self._pending.checks):
+            logits_b = self._model_b(batch)
+        label_a, unlabel_a = ops.split_rows(logits_a, [lb, ub])
+        label_b, unlabel_b = ops.split_rows(logits_b, [lb, ub])
+        labels = labeled_target.squeeze(1)
+        io = stepio.CURRENT
+        with checks.deferred(self._pending.checks):
+            sup_a = supervised_loss(self._sup_criterion, label_a, labels, self.num_classes)
+            sup_b = supervised_loss(self._sup_criterion, label_b, labels, self.num_classes)
+            # the count rides in the read-back block as the integer it is; the host divides it by the pixels (_record)
+            count = None if io is None else io.out("agree", (1,), torch.int64)
+            if self._on_labeled:
+                cross, _ = ops.softmax_cross_pseudo((label_a, unlabel_a), (label_b, unlabel_b), count)
+            else:
+                cross, _ = ops.softmax_cross_pseudo(unlabel_a, unlabel_b, count)
+        self._pending.put("sup_loss_b", sup_b)
+        return self._finish_step(sup_a, LinearLoss.of(cross), label_a, labels, more_loss=sup_b)
+
+    def _record(self, host: dict, inter: Tensor, union: Tensor, label_group) -> None:
+        super()._record(host, inter, union, label_group)
+        # ``agree``: the block's extra field, handed through by ``_Pending.wait``; records arrive in the order of the iterations
+        self.meters["agreement"].add(int(host["agree"][0]) / self._pixels_sent.pop(0))
 
 
 class MIDLTrainEpocher(UDATrainEpocher):

@@ -2,9 +2,10 @@
 
 Drop-in surface: ``trainer_zoos = {partial, uda, iic, udaiic}`` (+ ``meanteacher``, the reference's ContrastTrainerMT, and ``midl`` and
 ``entmin``, the ``MIDLPaperParameters`` and ``EntropyMinParameters`` sections' trainers, ``vat``, virtual adversarial training on the
-wheel's ``VATLoss``, ``ict``, interpolation consistency training on the Mean Teacher, ``uamt``, the uncertainty-aware Mean Teacher, and ``contrast`` and ``contrastdecoder``, the
-encoder and decoder stages of the reference's contrastive pre-training), the keyword-only constructor, ``init()``,
-``start_training()``, ``inference(checkpoint)``, ``set_feature_positions`` and the attribute names the checkpoint tree is
+wheel's ``VATLoss``, ``ict``, interpolation consistency training on the Mean Teacher, ``uamt``, the uncertainty-aware Mean Teacher,
+``cps``, cross pseudo supervision of two trainable networks, and ``contrast`` and ``contrastdecoder``, the encoder and decoder
+stages of the reference's contrastive pre-training), the keyword-only constructor, ``init()``, ``start_training()``,
+``inference(checkpoint)``, ``set_feature_positions`` and the attribute names the checkpoint tree is
 keyed by (``_model``, ``_optimizer``, ``_scheduler``, ``_projector_wrappers``, ``_IIDSegWrapper``, ``_storage`` ...; the
 tree itself is pinned by ``tests/golden/trainer_io.npz``).  Config sections are the ones of ``config/semi.yaml``.
 
@@ -367,6 +368,46 @@ class UAMTTrainer(MeanTeacherTrainer):
                              **self._epoch_args())
 
 
+class CPSTrainer(SemiTrainer):
+    """``cps``: cross pseudo supervision (Chen et al., CVPR 2021) -- two segmentation networks, ``_model`` (A) and ``_model_b`` (B, a
+    second ``UNet(**Arch)`` with its own initialisation), trained together: each on the supervised loss of the labeled batch and, with
+    ``CPSParameters.weight``, on the cross entropy against the OTHER network's hard prediction (over every image with ``on_labeled``,
+    the paper's form; over the unlabeled ones only without).  Both networks' parameters sit in the one fused optimiser.  The section is
+    optional: missing keys take the class's defaults.  Checkpoints carry ``_model_b``.  Validation, test and ``inference`` evaluate
+    network A, as in the paper.  ``Pretrained=`` loads network A only: B keeps its own initialisation, the difference between the two
+    being what the method feeds on.  Semantics: DESIGN.md section 30."""
+
+    DEFAULTS = dict(weight=1.5, on_labeled=True)
+    NAME = "cps"
+
+    @classmethod
+    def parameters(cls, configuration) -> dict:
+        """``CPSParameters`` of a configuration over the defaults; an unknown key is a ``KeyError``, a negative weight a ``ValueError``."""
+        section = dict((configuration or {}).get("CPSParameters") or {})
+        unknown = sorted(set(section) - set(cls.DEFAULTS))
+        if unknown:
+            raise KeyError(f"CPSParameters: unknown keys {unknown}; known: {sorted(cls.DEFAULTS)}")
+        merged = {**cls.DEFAULTS, **section}
+        if not float(merged["weight"]) >= 0.0:
+            raise ValueError(f"CPSParameters.weight={merged['weight']}: must not be negative")
+        return dict(weight=float(merged["weight"]), on_labeled=bool(merged["on_labeled"]))
+
+    def _init(self) -> None:
+        super()._init()
+        from contrastyou.arch import UNet
+        params = self.parameters(self._config)
+        self._reg_weight, self._on_labeled = params["weight"], params["on_labeled"]
+        self._model_b = UNet(**self._config["Arch"])
+        self._model_b.train()
+
+    def _trainable(self):
+        return chain(self._model.parameters(), self._model_b.parameters())
+
+    def _make_epocher(self):
+        return E.CPSEpocher(self._model, self._model_b, self._optimizer, self._labeled_loader, self._unlabeled_loader, self._sup_criterion,
+                            reg_weight=self._reg_weight, on_labeled=self._on_labeled, **self._epoch_args())
+
+
 class MIDLTrainer(UDATrainer):
     """``midl``: ``UDARegCriterion.weight`` x consistency + ``MIDLPaperParameters.iic_weight`` x the local mutual information of the
     network's output (``IIDSegmentationSmallPathLoss(padding, patch_size)`` on softmax(flip(f(x))) and softmax(f(flip(x)))); the
@@ -584,4 +625,4 @@ class ContrastDecoderTrainer(ContrastTrainer):
 
 trainer_zoos = {"partial": SemiTrainer, "uda": UDATrainer, "iic": IICTrainer, "udaiic": UDAIICTrainer, "meanteacher": MeanTeacherTrainer,
                 "midl": MIDLTrainer, "entmin": EntropyMinTrainer, "vat": VATTrainer, "contrast": ContrastTrainer,
-                "contrastdecoder": ContrastDecoderTrainer, "ict": ICTTrainer, "uamt": UAMTTrainer}
+                "contrastdecoder": ContrastDecoderTrainer, "ict": ICTTrainer, "uamt": UAMTTrainer, "cps": CPSTrainer}
